@@ -6,8 +6,15 @@ Workload: seeded symmetric hash-window matrix, n = 1e7, ~100
 device (no host copy).  One bench "step" = one fixed-length RBL run: rbl_start (A*Omega +
 QR) and the m_max = ceil(1200/b) = 38 block iterations of RBL_gpu.jl:162 with convergence
 checks off (partial-reorth cost grows with i, so the step range is fixed).
-value = block iterations per second of the whole job.  Time-to-k=20 (convergence on, from
-start through Ritz vectors) is reported beside it.
+value = block iterations per second of the whole job; ms_per_step = the milliseconds one
+step (one fixed-length run) took.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what that figure needs: it
+generates the matrix, runs W untimed and N timed steps, writes the last timed step's outputs
+when --dump-outputs DIR is given, and prints the line.  With --full it goes on to everything
+else the line can carry: the stage-timer pass of the same runs, time-to-k=20 (convergence
+on, from start through Ritz vectors) on the planted and on a slowly decaying spectrum, the
+C4b R-MAT / C3 circuit / wide-band / C5 sub-records and the CPU baseline.
 
 Multi-GPU: one process per GPU (torch.distributed.run); rows are partitioned over ranks
 (strong scaling: n fixed), SpMM halos and Gram all-reduces go over RCCL inside
@@ -45,6 +52,16 @@ def parse():
                          "torch.distributed.run with N processes (before any GPU call)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed runs also measure everything else the line can "
+                         "carry: the stage-timer pass of the same runs (stage_ms_per_run), the "
+                         "time-to-k runs, the C4b / C3 / wide-band / C5 sub-records and the CPU "
+                         "baseline.  Off by default: a plain run generates the matrix, warms up, "
+                         "times --steps runs and prints the line (those entries null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed runs write what the last of them computed to DIR/<name>.npy "
+                         "(float64; see dump_outputs): the same arguments give the same inputs, so "
+                         "two builds can be compared array for array")
     ap.add_argument("--n", type=int, default=10_000_000)
     ap.add_argument("--b", type=int, default=32)
     ap.add_argument("--k", type=int, default=20)
@@ -366,13 +383,53 @@ def cpu_seconds() -> float:
     return ru.ru_utime + ru.ru_stime
 
 
-def measure(ctx, args, matrix, K, W, nloc, nnz_loc, world, barrier, allmax, gather=None):
+DUMP_ROWS = 4096             # basis rows sampled by --dump-outputs (seeded, the same every run)
+
+
+def dump_outputs(ctx, args, info, dirname):
+    """--dump-outputs: what the last timed run computed, as float64 `.npy` files in `dirname`
+    (a few MB).  The timed path is a fixed-length rbl.lanczos (convergence checks off, no Ritz
+    vectors); what its caller receives are the blocks of the band matrix T:
+      T_A.npy          (m, b, b)  A_i = Q_i^T A Q_i of every block step
+      T_B.npy          (m, b, b)  B_{i+1} (upper triangular) of every block step
+    and what it leaves on the device is the Krylov basis, of which a fixed sample is kept:
+      ritz_values.npy  (k,)       the k largest-|lambda| eigenvalues of T (descending |lambda|),
+                                  solved on the host from the two arrays above
+      Q_rows.npy       (DUMP_ROWS,) the sampled local rows (seeded by --seed; rank 0's rows)
+      Q_blocks.npy     (3,)       the basis blocks sampled (1-based): first, middle, last
+      Q_sample.npy     (3, DUMP_ROWS, b)  those rows of those blocks
+    The matrix, the start block and the sample depend on the arguments only."""
+    from rbl.host import TBand, eig_topk
+    os.makedirs(dirname, exist_ok=True)
+    b = args.b
+    A, B = np.stack(info.trace_A), np.stack(info.trace_B)
+    T = TBand(b, len(A))
+    for j in range(len(A)):                    # as rbl.lanczos fills it
+        T.insert_A(A[j])
+        T.insert_B(B[j], j + 1)
+    D, _ = eig_topk(T.view(), min(args.k, b * len(A)))
+    nloc = ctx.matrix_info()[2] - ctx.matrix_info()[1]
+    rows = np.sort(np.random.default_rng(args.seed).choice(nloc, size=min(nloc, DUMP_ROWS),
+                                                           replace=False))
+    nb = ctx.num_blocks()
+    blocks = np.array(sorted({1, (nb + 1) // 2, nb}), dtype=np.int64)
+    Q = np.stack([np.ascontiguousarray(ctx.get_block(int(j))[rows]) for j in blocks])
+    for name, arr in (("T_A", A), ("T_B", B), ("ritz_values", D[::-1]), ("Q_rows", rows),
+                      ("Q_blocks", blocks), ("Q_sample", Q)):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
+def measure(ctx, args, matrix, K, W, nloc, nnz_loc, world, barrier, allmax, gather=None,
+            full=True, dump_dir=None):
     """W untimed + K timed fixed-length runs (rbl_start + m_max block steps, convergence checks
     off) on the matrix the context holds; the max over ranks of the timed region, the stage
     times (hipEvents) and the SpMM / partial-reorth rooflines priced from them.  On several
     ranks (`gather`: an all-gather of a Python object) every rank's own record as well: its
     run times, its stage split, its collectives (counts, bytes, host and device time per
-    call), and the CPU time its process used against the CPUs it may run on."""
+    call), and the CPU time its process used against the CPUs it may run on.
+    `full` False (a plain run of the headline): the timed region only — no stage-timer pass
+    (stage and per_rank come back None).  `dump_dir`: the last timed run's outputs are written
+    there (dump_outputs) once the timed region is over."""
     import rbl
     from rbl import _lib
     n, b, k = args.n, args.b, args.k
@@ -383,13 +440,17 @@ def measure(ctx, args, matrix, K, W, nloc, nnz_loc, world, barrier, allmax, gath
                    6: "segmented-gather", 7: "column-panel-csr"}[spmm_kid]
 
     host = {"start": 0.0, "enqueue": 0.0, "fetch_wait": 0.0}
+    # --dump-outputs: the runs keep the A_i / B_{i+1} they fetch (lanczos' trace: 2 m_max copies
+    # of a b x b block per run, microseconds), which is what a caller of this path receives
+    trace = dump_dir is not None
 
     def one_run():
         _, _, info = rbl.lanczos(ctx, k, b, kryl_sz=args.kryl, seed=args.seed + 1, check=False,
-                                 ritz=False, basis_bits=args.basis_bits)
+                                 ritz=False, basis_bits=args.basis_bits, trace=trace)
         host["start"] += info.start_ms
         host["enqueue"] += info.enqueue_ms
         host["fetch_wait"] += info.fetch_ms
+        return info
 
     for w_ in range(W):
         one_run()
@@ -411,7 +472,7 @@ def measure(ctx, args, matrix, K, W, nloc, nnz_loc, world, barrier, allmax, gath
     t0 = time.perf_counter()
     marks = [t0]
     for k_ in range(K):
-        one_run()  # (returns once the run's last block step has been fetched)
+        last_info = one_run()  # (returns once the run's last block step has been fetched)
         marks.append(time.perf_counter())
         progress(f"{matrix} n={n} b={b}: timed run {k_ + 1}/{K} {(marks[-1] - marks[-2]) * 1e3:.1f} ms")
     ctx.synchronize()
@@ -430,25 +491,30 @@ def measure(ctx, args, matrix, K, W, nloc, nnz_loc, world, barrier, allmax, gath
                   "max": round(runs_ms[-1], 2)} if runs_ms else None
     host_timed = dict(host)
     stage_timed = ctx.timers()  # "AQ" and "part reorth" of the timed region
+    if dump_dir is not None and K:
+        dump_outputs(ctx, args, last_info, dump_dir)
+        progress(f"outputs of timed run {K}/{K} written to {dump_dir}")
     ctx.set_option(_lib.RBL_OPT_TIMERS, 1)
-    barrier()
-    ctx.synchronize()
-    ctx.reset_timers()
-    ctx.comm_stats(reset=True)
-    barrier()
-    t1 = time.perf_counter()
-    for k_ in range(K):
-        one_run()
-        progress(f"{matrix} n={n} b={b}: stage-timer run {k_ + 1}/{K}")
-    ctx.synchronize()
-    local_staged = time.perf_counter() - t1
-    barrier()
-    elapsed_staged = allmax(time.perf_counter() - t1)
-    comm_staged = ctx.comm_stats(times=True)
+    stage = elapsed_staged = None
+    if full:
+        barrier()
+        ctx.synchronize()
+        ctx.reset_timers()
+        ctx.comm_stats(reset=True)
+        barrier()
+        t1 = time.perf_counter()
+        for k_ in range(K):
+            one_run()
+            progress(f"{matrix} n={n} b={b}: stage-timer run {k_ + 1}/{K}")
+        ctx.synchronize()
+        local_staged = time.perf_counter() - t1
+        barrier()
+        elapsed_staged = allmax(time.perf_counter() - t1)
+        comm_staged = ctx.comm_stats(times=True)
+        stage = ctx.timers()
     host = host_timed
-    stage = ctx.timers()
     per_rank = None
-    if gather is not None and world > 1 and K:
+    if full and gather is not None and world > 1 and K:
         try:
             aff = len(os.sched_getaffinity(0))
         except (AttributeError, OSError):
@@ -488,7 +554,6 @@ def measure(ctx, args, matrix, K, W, nloc, nnz_loc, world, barrier, allmax, gath
     host = host_timed
     iters = K * m_max
     value = iters / elapsed
-    stage_per_run = {s: v / K for s, v in stage.items()}
 
     # ---- roofline: SpMM (HBM) and partial reorth (fp64 MFMA), live from HIP events ----
     spmm_launches = K * (m_max + 1)               # rbl_start + one per block step
@@ -593,7 +658,7 @@ def measure(ctx, args, matrix, K, W, nloc, nnz_loc, world, barrier, allmax, gath
     return {"elapsed": elapsed, "stage": stage, "value": value, "roofline": roofline,
             "per_rank": per_rank,
             "host_ms_per_run": host_ms,
-            "stage_pass_ms_per_run": round(elapsed_staged * 1e3 / K, 2) if K else None,
+            "stage_pass_ms_per_run": round(elapsed_staged * 1e3 / K, 2) if K and full else None,
             "roofline_secondary": roofline2, "spmm_kernel": spmm_kernel,
             "comm_per_step": comm_per_step, "m_max": m_max, "run_ms": run_spread}
 
@@ -776,16 +841,19 @@ def main():
     ctx.set_option(_lib.RBL_OPT_FUSE, args.fuse)
     m_max = rbl.rbl_gpu.max_steps_for(args.kryl, b)
     meas = measure(ctx, args, args.matrix, args.steps, args.warmup, nloc, nnz_loc, world,
-                   barrier, allmax, gather_obj)
+                   barrier, allmax, gather_obj, full=args.full,
+                   dump_dir=args.dump_outputs if rank == 0 else None)
     K = args.steps
     elapsed, stage, value = meas["elapsed"], meas["stage"], meas["value"]
-    stage_per_run = {s: v / K for s, v in stage.items()}
+    # (the stage split comes from the stage-timer pass: --full)
+    stage_per_run = {s: v / K for s, v in stage.items()} if stage is not None else None
     roofline, roofline2 = meas["roofline"], meas["roofline_secondary"]
+    full = args.full    # everything below the headline's timed runs is measured only with --full
 
     # ---- time-to-k (convergence on, start -> converged Ritz vectors) ----
-    progress("time-to-k")
     ttk = None
-    if not args.no_ttk:
+    if full and not args.no_ttk:
+        progress("time-to-k")
         barrier()
         ctx.synchronize()
         ctx.reset_timers()
@@ -808,7 +876,7 @@ def main():
 
     # ---- time-to-k on a slowly decaying spectrum (same generator and n, another plant) ----
     ttk_slow = None
-    if not args.no_ttk and not args.no_ttk_slow and args.matrix == "hashwindow":
+    if full and not args.no_ttk and not args.no_ttk_slow and args.matrix == "hashwindow":
         slow_plant = np.array([12.0 + 0.25 * (2 * k + 1 - l) for l in range(1, 2 * k + 1)])
         ctx.gen_hashwindow(n, args.halfwidth, args.density, args.seed, slow_plant)
         # one untimed start + step on the run's own plan (m_max blocks, so the timed run reuses
@@ -857,28 +925,29 @@ def main():
             return {"error": f"{type(e).__name__}: {e}"}
 
     rmat_rec = None
-    if args.matrix == "hashwindow" and args.rmat_steps > 0 and args.basis_bits == 64:
+    if full and args.matrix == "hashwindow" and args.rmat_steps > 0 and args.basis_bits == 64:
         progress("C4b sub-record")
         rmat_rec = guarded(rmat_subrecord, ctx, args, plant, world, barrier, allmax, allsum,
                            allgather_i64, gather_obj, shared_gpu)
 
     # ---- BASELINE config 3's shape: the circuit-like matrix at G3_circuit's n, b = 16 ----
     c3_rec = None
-    if args.matrix == "hashwindow" and args.c3_steps > 0 and args.basis_bits == 64:
+    if full and args.matrix == "hashwindow" and args.c3_steps > 0 and args.basis_bits == 64:
         progress("C3 sub-record")
         c3_rec = guarded(c3_subrecord, ctx, args, world, barrier, allmax, allsum, allgather_i64,
                          gather_obj)
 
     # ---- a wide band (the FEM / circuit orderings benchmark.jl loads): the column panels ----
     wide_rec = None
-    if args.matrix == "hashwindow" and args.wide_steps > 0 and args.basis_bits == 64 and args.b == 32:
+    if (full and args.matrix == "hashwindow" and args.wide_steps > 0 and args.basis_bits == 64
+            and args.b == 32):
         progress("wide-band sub-record")
         wide_rec = guarded(wide_subrecord, ctx, args, plant, world, barrier, allmax, allsum,
                            allgather_i64, gather_obj)
 
     # ---- CPU baseline: the oracle (port of RBL.jl) on a bounded sample, rank 0, N = 1 ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress("CPU baseline")
         cpu = cpu_baseline(args, m_max, plant)
 
@@ -922,9 +991,11 @@ def main():
                    **({"fuse": args.fuse} if args.fuse != 7 else {})},
         "roofline": roofline,
         "roofline_secondary": roofline2,
-        "stage_ms_per_run": {s: round(v, 3) for s, v in stage_per_run.items()},
+        "full": full,
+        "stage_ms_per_run": ({s: round(v, 3) for s, v in stage_per_run.items()}
+                             if stage_per_run is not None else None),
         "host_ms_per_run": meas["host_ms_per_run"],
-        # the same K runs again with the stage timers on (stage_ms_per_run and the rooflines)
+        # --full: the same K runs again with the stage timers on (stage_ms_per_run, per_rank)
         "stage_pass_ms_per_run": meas["stage_pass_ms_per_run"],
         "time_to_k": ttk,
         "time_to_k_slow_spectrum": ttk_slow,
@@ -948,7 +1019,7 @@ def main():
                 out = out[os.write(line_fd, out):]
 
     # ---- BASELINE config 5: n = 5e7, fp32 basis, on >= 2 ranks (no spill) ----
-    if (args.matrix == "hashwindow" and args.c5_steps > 0 and args.basis_bits == 64
+    if (full and args.matrix == "hashwindow" and args.c5_steps > 0 and args.basis_bits == 64
             and world >= args.c5_min_ranks):
         progress("C5 sub-record")
         try:

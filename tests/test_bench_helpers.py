@@ -106,3 +106,63 @@ def test_rank_arrays(bench):
     assert out["slowest_rank"] == 1
     assert out["host_cpu"]["cpu_s_per_run_all_ranks"] == 1.0
     assert bench.rank_arrays([]) is None
+
+
+def test_plain_run_is_the_default(bench, monkeypatch):
+    """Without --full the run stops after the headline's timed steps; --dump-outputs is off."""
+    a = _args(bench, monkeypatch, ["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (4, 2)
+    a = _args(bench, monkeypatch, ["--full", "--dump-outputs", "somewhere"])
+    assert a.full and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_files(bench, monkeypatch, tmp_path):
+    """--dump-outputs: the T blocks as fetched, the Ritz values of the band they form (against a
+    dense eigensolve of the same T), and the seeded row sample of the first / middle / last basis
+    block — float64 arrays, the same rows for the same seed."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "gpu-randomized-block-lanczos_amd"))
+    from rbl.rbl_gpu import RBLInfo
+    b, m, k, nloc = 4, 5, 3, 10_000
+    rng = np.random.default_rng(3)
+    info = RBLInfo()
+    for _ in range(m):
+        S = rng.standard_normal((b, b))
+        info.trace_A.append(np.asfortranarray(S + S.T))
+        info.trace_B.append(np.asfortranarray(np.triu(rng.standard_normal((b, b)))))
+
+    class Ctx:
+        def matrix_info(self):
+            return nloc, 0, nloc, 0
+
+        def num_blocks(self):
+            return m + 1
+
+        def get_block(self, j):
+            return np.asfortranarray(np.arange(nloc)[:, None] * 100.0 + j + np.zeros((1, b)))
+
+    a = _args(bench, monkeypatch, ["--b", str(b), "--k", str(k), "--seed", "11"])
+    for d in ("one", "two"):
+        bench.dump_outputs(Ctx(), a, info, str(tmp_path / d))
+    got = {f[:-4]: np.load(tmp_path / "one" / f) for f in sorted(os.listdir(tmp_path / "one"))}
+    assert sorted(got) == ["Q_blocks", "Q_rows", "Q_sample", "T_A", "T_B", "ritz_values"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) < 64e6
+    assert np.array_equal(got["T_A"], np.stack(info.trace_A))
+    assert np.array_equal(got["T_B"], np.stack(info.trace_B))
+    T = np.zeros((m * b, m * b))
+    for j in range(m):
+        T[j * b:(j + 1) * b, j * b:(j + 1) * b] = info.trace_A[j]
+        if j + 1 < m:   # B_{j+1} couples blocks j and j + 1
+            T[(j + 1) * b:(j + 2) * b, j * b:(j + 1) * b] = info.trace_B[j]
+            T[j * b:(j + 1) * b, (j + 1) * b:(j + 2) * b] = info.trace_B[j].T
+    w = np.linalg.eigvalsh(T)
+    w = w[np.argsort(-np.abs(w))][:k]
+    assert np.allclose(got["ritz_values"], w, rtol=1e-12, atol=0)
+    assert list(got["Q_blocks"]) == [1, 3, 6]
+    rows = got["Q_rows"].astype(np.int64)
+    assert len(rows) == bench.DUMP_ROWS and len(set(rows)) == len(rows) and rows.max() < nloc
+    assert got["Q_sample"].shape == (3, bench.DUMP_ROWS, b)
+    assert np.array_equal(got["Q_sample"][1], rows[:, None] * 100.0 + 3 + np.zeros((1, b)))
+    for f in os.listdir(tmp_path / "one"):
+        assert np.array_equal(np.load(tmp_path / "one" / f), np.load(tmp_path / "two" / f))

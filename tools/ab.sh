@@ -21,7 +21,7 @@ for rep in $(seq 1 "$REPS"); do
     if [ "$lib" != tree ]; then export RBL_LIB=$PWD/tools/variants/$lib/librbl_hip.so; fi
     safe=$(echo "$v" | tr '=:/' '__-')
     out=gpurun_out/${tag}_${safe}_${rep}.json
-    env ${envs[@]+"${envs[@]}"} timeout -k 10 600 python bench.py $args > "$out" 2> "${out%.json}.err" || exit 1
+    env ${envs[@]+"${envs[@]}"} timeout -k 10 600 python bench.py --full $args > "$out" 2> "${out%.json}.err" || exit 1
     python - "$v" "$out" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -1,11 +1,13 @@
-# Bench lines for every workload the repo claims numbers for (C4a fp64 / fp32 basis, C4b R-MAT,
-# C2, host spill); each to gpurun_out/ev_<name>.json.  Usage: bash tools/evidence.sh
+# Bench lines (--full: stage split, time-to-k, sub-records) for every workload the repo claims
+# numbers for (C4a fp64 / fp32 basis, C4b R-MAT, C2, host spill); each to $OUT/ev_<name>.json
+# (OUT defaults to bench_out).  Usage: bash tools/evidence.sh
 set -u
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 run() {
   name=$1; shift
-  timeout -k 10 600 python bench.py "$@" > gpurun_out/ev_$name.json 2> gpurun_out/ev_$name.err || exit $?
-  echo "$name: $(python3 -c "import json;d=json.load(open('gpurun_out/ev_$name.json'));print(d['value'], d['unit'])")"
+  timeout -k 10 600 python bench.py --full "$@" > "$OUT/ev_$name.json" 2> "$OUT/ev_$name.err" || exit $?
+  echo "$name: $(python3 -c "import json,sys;d=json.load(open(sys.argv[1]));print(d['value'], d['unit'])" "$OUT/ev_$name.json")"
 }
 run c4a_fp64 --steps 3 --no-cpu-baseline
 run c4a_fp32 --basis-bits 32 --steps 3 --no-cpu-baseline

@@ -27,7 +27,7 @@ def main():
     out = {k: {"launches": n[k], "avg_us": round(dur[k] / n[k] / 1e3, 1),
                "clock_ghz": round(gui[k] / 8 / dur[k], 3)}
            for k in sorted(dur, key=lambda k: -dur[k]) if dur[k] > 0 and gui[k] > 0}
-    res = {"method": "rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT over `bench.py --steps 1 --warmup 0 "
+    res = {"method": "rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT over `bench.py --full --steps 1 --warmup 0 "
                      "--no-cpu-baseline --no-ttk`; clock = GRBM_GUI_ACTIVE / 8 / wall",
            "config": {"n": 10_000_000, "b": 32, "workload": "C4a"}, "kernels": out}
     txt = json.dumps(res, indent=1)

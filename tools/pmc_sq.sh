@@ -3,7 +3,7 @@
 set -u
 mkdir -p gpurun_out/sq
 export TMPDIR=/tmp
-B="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-ttk"
+B="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-ttk"
 timeout -k 10 120 rocprofv3 -L > gpurun_out/sq/counters.txt 2>&1 || true
 rc=0
 i=0

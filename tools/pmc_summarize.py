@@ -66,7 +66,7 @@ def main():
     # the partial-reorth pair: the Gram and the 64- (b = 32) or 32-column (b = 16) update
     upd = ("k_tsmm44<32, 64,", "k_tsmm44f") if wb == 32 else ("k_tsmm44<16, 32,",)
     reo = {k: v for k, v in kern.items() if k.startswith((f"k_gram44<{wb}, 2",) + upd)}
-    # bench.py --steps 1 --warmup 0 runs the job once timed and (since round 6) once more with
+    # bench.py --full --steps 1 --warmup 0 runs the job once timed and (since round 6) once more with
     # the stage timers: count the runs by the Gram's launches (len(range(4, m + 1, 2)) per run)
     per_run = len(range(4, wm + 1, 2))
     gl = sum(v["launches"] for k, v in reo.items() if k.startswith(f"k_gram44<{wb}, 2"))
@@ -94,7 +94,7 @@ def main():
         "part_reorth_hbm_bytes_per_run": reorth_bytes,
         "kernels": kern,
         "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over "
-                  "`bench.py --steps 1 --warmup 0`; KB x 1024 x per-width calibration factor "
+                  "`bench.py --full --steps 1 --warmup 0`; KB x 1024 x per-width calibration factor "
                   "(tools/pmc_calib.hip, 2 GiB streams)",
     }
     txt = json.dumps(res, indent=1)
