@@ -220,6 +220,20 @@ void spmm_seg_tier(const CsrDev::Tier& T, const double* Q, int64_t col_off, int 
 // columns — the received pushed partials added to their rows.
 void push_add(const int64_t* rows, const int64_t* ptr, const int64_t* slot, int64_t nrows,
               const double* recv, int b, double* U, hipStream_t s);
+// --- spmm_rect.hip: rectangular sparse B (rbl_set_matrix_normal) ---------------------------
+// One orientation of B is a CSR with its task table (a CsrDev::Tier: rows packed / cut as for
+// the segmented gather, with these limits; scratch holds kWave doubles per segment slot).
+constexpr int64_t kRectSegLen = 1024;  // nonzeros per long-row segment
+constexpr int64_t kRectPack = 512;     // nonzeros per packed short-row task (<= 64 rows)
+// The other orientation of a CSR (`rows` rows, ids < cols, every row strictly ascending), built
+// on the device: tptr (cols + 1), tind / tval (nnz), every row of the result ascending — the
+// same arrays whatever order the fill ran in.  nnz < 2^31.  Returns 0 or a hipError_t.
+int rect_transpose(int64_t rows, int64_t cols, int64_t nnz, const int64_t* ptr, const int32_t* ind,
+                   const double* val, int64_t* tptr, int32_t* tind, double* tval, hipStream_t s);
+// out = T Q (- Qprev Bi^T if Qprev) (columns scaled by scale[c] if scale): Q, out, Qprev
+// row-major with b columns, any b >= 1; out has T's rows, Q the rows T's ids index.
+void spmm_rect(const CsrDev::Tier& T, const double* Q, int b, double* out, const double* Qprev,
+               const double* Bi, const double* scale, hipStream_t s);
 // spmm_panel.hip: column-panel CSR kernel for wide bands (b = 32, Q rows [q_lo, q_hi)); false
 // if not applicable.  panel_width(): Q rows per panel.
 bool spmm_panel(const CsrDev& A, const double* Qin, int64_t col_off, int b, double* U,

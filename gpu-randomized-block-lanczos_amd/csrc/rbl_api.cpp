@@ -124,6 +124,14 @@ struct rbl_ctx {
   int64_t dense_panels = 0;
   double* d_qfull = nullptr;
   int qfull_cols = 0;         // columns d_qfull was sized for
+  // rectangular sparse B, m x n (rbl_set_matrix_normal): both orientations as CSR with their
+  // task tables — [0] B's rows (column ids), [1] B^T's rows (row ids) — for the gather pair of
+  // spmm_rect.hip; the Krylov operator is B^T B on n rows, Y = B Q_i passes through d_rect_y
+  bool rect = false;
+  int64_t rect_m = 0;
+  SegTierBuf rect_side[2];
+  double* d_rect_y = nullptr;  // m x rect_y_cols
+  int rect_y_cols = 0;
   int64_t ntiles = 0, tiles_per_wg = 0;
   bool window_ok16 = false, window_ok32 = false;
   bool band_ok16 = false, band_ok32 = false;
@@ -386,8 +394,11 @@ CsrDev csr(rbl_ctx* ctx) {
 }
 
 // Task table of the segmented gather (spmm.hip variant 5): short rows packed into tasks of
-// <= kSegPack nonzeros and <= 64 rows, rows over kSegLen nonzeros cut into segments.
-int build_seg(rbl_ctx* ctx, const std::vector<int64_t>& rp, rbl_ctx::SegTierBuf& out) {
+// <= kSegPack nonzeros and <= 64 rows, rows over kSegLen nonzeros cut into segments.  The
+// rectangular gather pair (spmm_rect.hip) builds its two tables here with its own limits and
+// scratch_w = 64 doubles per segment slot.
+int build_seg(rbl_ctx* ctx, const std::vector<int64_t>& rp, rbl_ctx::SegTierBuf& out,
+              int64_t seg_len = kSegLen, int64_t pack = kSegPack, int scratch_w = 32) {
   const int64_t m = (int64_t)rp.size() - 1;
   if (m <= 0) return RBL_OK;
   std::vector<int64_t> trow, slot_k0, lrow, lslot;
@@ -404,18 +415,18 @@ int build_seg(rbl_ctx* ctx, const std::vector<int64_t>& rp, rbl_ctx::SegTierBuf&
   };
   for (int64_t r = 0; r < m; ++r) {
     const int64_t d = rp[r + 1] - rp[r];
-    if (d > kSegLen) {
+    if (d > seg_len) {
       flush();
       lrow.push_back(r);
       lslot.push_back((int64_t)slot_k0.size());
-      for (int64_t k = rp[r]; k < rp[r + 1]; k += kSegLen) {
+      for (int64_t k = rp[r]; k < rp[r + 1]; k += seg_len) {
         trow.push_back(r);
         tinfo.push_back(-(int32_t)(slot_k0.size() + 1));
         slot_k0.push_back(k);
       }
       continue;
     }
-    if (cur_rows && (cur_nnz + d > kSegPack || cur_rows == 64)) flush();
+    if (cur_rows && (cur_nnz + d > pack || cur_rows == 64)) flush();
     if (!cur_rows) cur_r0 = r;
     ++cur_rows;
     cur_nnz += d;
@@ -430,7 +441,7 @@ int build_seg(rbl_ctx* ctx, const std::vector<int64_t>& rp, rbl_ctx::SegTierBuf&
   HIPC(hipMalloc(&out.slot_k0, slot_k0.size() * sizeof(int64_t)));
   HIPC(hipMalloc(&out.lslot, lslot.size() * sizeof(int64_t)));
   HIPC(hipMalloc(&out.lrow, std::max<size_t>(lrow.size(), 1) * sizeof(int64_t)));
-  HIPC(hipMalloc(&out.scratch, std::max<size_t>(slot_k0.size() - 1, 1) * 32 * sizeof(double)));
+  HIPC(hipMalloc(&out.scratch, std::max<size_t>(slot_k0.size() - 1, 1) * scratch_w * sizeof(double)));
   HIPC(hipMemcpy(out.trow, trow.data(), trow.size() * sizeof(int64_t), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(out.tinfo, tinfo.data(), tinfo.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(out.slot_k0, slot_k0.data(), slot_k0.size() * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -1460,7 +1471,36 @@ size_t gram_slab_elems(const rbl_ctx* ctx, int b, int max_blocks, int basis_bits
   return slab;
 }
 
-bool has_matrix(const rbl_ctx* ctx) { return ctx->d_rowptr || ctx->dense; }
+bool has_matrix(const rbl_ctx* ctx) { return ctx->d_rowptr || ctx->dense || ctx->rect; }
+
+// one orientation of a rectangular B as the kernels take it (0: B's rows, 1: B^T's rows)
+CsrDev::Tier rect_tier(const rbl_ctx* ctx, int side) {
+  const auto& T = ctx->rect_side[side];
+  CsrDev::Tier D;
+  D.rowptr = T.rowptr;
+  D.col = T.col;
+  D.val = T.val;
+  D.ntasks = T.ntasks;
+  D.nlong = T.nlong;
+  D.trow = T.trow;
+  D.tinfo = T.tinfo;
+  D.slot_k0 = T.slot_k0;
+  D.lrow = T.lrow;
+  D.lslot = T.lslot;
+  D.scratch = T.scratch;
+  return D;
+}
+// the m x b work block Y = B Q_i of the normal operator
+int ensure_rect_y(rbl_ctx* ctx, int b) {
+  if (ctx->d_rect_y && ctx->rect_y_cols >= b) return RBL_OK;
+  HIPC(hipStreamSynchronize(ctx->stream));
+  hipFree(ctx->d_rect_y);
+  ctx->d_rect_y = nullptr;
+  ctx->rect_y_cols = 0;
+  HIPC(hipMalloc(&ctx->d_rect_y, (size_t)ctx->rect_m * b * sizeof(double)));
+  ctx->rect_y_cols = b;
+  return RBL_OK;
+}
 
 // fp32 basis: the band-tile SpMM and the 3-term update read the fp32 blocks directly
 bool direct32_ok(const rbl_ctx* ctx, int b) {
@@ -1510,6 +1550,14 @@ int apply_A(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* U, cons
             const double* lfix_c = nullptr, double* lfix_q = nullptr, int64_t lf_lo = 0,
             int64_t lf_hi = 0, hipEvent_t seg_wait = nullptr) {
   if (ctx->nloc <= 0) return 0;
+  if (ctx->rect) {  // B^T (B Q_i): two gather passes, the 3-term epilogue fused into the second
+    CHK(ensure_rect_y(ctx, b));
+    spmm_rect(rect_tier(ctx, 0), Qin + (0 - off) * b, b, ctx->d_rect_y, nullptr, nullptr, nullptr,
+              ctx->stream);
+    spmm_rect(rect_tier(ctx, 1), ctx->d_rect_y, b, U, Qprev, Bi, nullptr, ctx->stream);
+    ctx->path_stats[RBL_PATH_SPMM] += 1;
+    return 0;
+  }
   if (ctx->csr_dropped && rbl_spmm_kernel_for(ctx, b) != 5)
     return fail(ctx, RBL_ERR_STATE, "the CSR was released (RBL_OPT_KEEP_CSR = 0): only the band-tile "
                                     "SpMM (b in {16, 32}) can run");
@@ -2163,6 +2211,10 @@ void free_matrix(rbl_ctx* ctx) {
   hipFree(ctx->d_seg_scratch); ctx->d_seg_scratch = nullptr;
   ctx->seg_ntasks = ctx->seg_nlong = 0;
   free_tiers(ctx);
+  for (auto& T : ctx->rect_side) free_seg(T, true);
+  hipFree(ctx->d_rect_y); ctx->d_rect_y = nullptr; ctx->rect_y_cols = 0;
+  ctx->rect = false;
+  ctx->rect_m = 0;
   hipFree(ctx->d_dense); ctx->d_dense = nullptr;
   hipFree(ctx->d_qfull); ctx->d_qfull = nullptr; ctx->qfull_cols = 0;
   ctx->dense = false;
@@ -2805,6 +2857,149 @@ int rbl_gen_matrix_rmat(rbl_ctx* ctx, int64_t n, int scale, int64_t edges, doubl
   return setup_halo(ctx);
 }
 
+int rbl_set_matrix_normal(rbl_ctx* ctx, int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* ptr,
+                          const int64_t* ind, const double* val, int index_base, int layout) {
+  if (!ctx || nrows < 1 || ncols < 1 || nnz < 0 || !ptr || (nnz && (!ind || !val)) ||
+      (index_base != 0 && index_base != 1) || (layout != 0 && layout != 1))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_normal: bad arguments");
+  if (ctx->nranks > 1)  // before any collective: no rank waits for another
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_normal: one rank only");
+  if (nrows > INT32_MAX || ncols > INT32_MAX)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_normal: nrows and ncols must be < 2^31 (int32 ids)");
+  if (nnz >= INT32_MAX)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_normal: nnz must be < 2^31 - 1 (the device transpose)");
+  // the arrays passed are the CSR of side P: B's rows (layout 0) or B^T's rows (layout 1, B's CSC)
+  const int P = layout;
+  const int64_t rows = P == 0 ? nrows : ncols, ids = P == 0 ? ncols : nrows;
+  if (ptr[rows] - ptr[0] != nnz || ptr[0] != index_base)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_normal: ptr does not span nnz entries");
+  std::vector<int64_t> rp(rows + 1);
+  for (int64_t i = 0; i <= rows; ++i) {
+    rp[i] = ptr[i] - index_base;
+    if (rp[i] < (i ? rp[i - 1] : 0) || rp[i] > nnz)
+      return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_normal: ptr not monotone");
+  }
+  std::vector<int32_t> ci(std::max<int64_t>(nnz, 1));
+  for (int64_t i = 0; i < rows; ++i)
+    for (int64_t e = rp[i]; e < rp[i + 1]; ++e) {
+      const int64_t c = ind[e] - index_base;
+      if (c < 0 || c >= ids) return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_normal: index out of range");
+      // strictly ascending (canonical: sorted, no duplicates) — the transpose's per-row order and
+      // its value lookup rely on it
+      if (e > rp[i] && c <= ci[e - 1])
+        return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_normal: indices must be strictly ascending "
+                                          "within each row (layout 0) / column (layout 1)");
+      ci[e] = (int32_t)c;
+    }
+  HIPC(hipSetDevice(ctx->device));
+  free_run(ctx);
+  free_matrix(ctx);
+  ctx->bounds = {0, ncols};
+  ctx->n = ncols;
+  ctx->r0 = 0;
+  ctx->r1 = ncols;
+  ctx->nloc = ncols;
+  ctx->nnz = nnz;
+  ctx->rect = true;
+  ctx->rect_m = nrows;
+  const size_t ne = (size_t)std::max<int64_t>(nnz, 1);
+  auto& S = ctx->rect_side[P];
+  auto& T = ctx->rect_side[1 - P];
+  HIPC(hipMalloc(&S.rowptr, (rows + 1) * sizeof(int64_t)));
+  HIPC(hipMalloc(&S.col, ne * sizeof(int32_t)));
+  HIPC(hipMalloc(&S.val, ne * sizeof(double)));
+  HIPC(hipMalloc(&T.rowptr, (ids + 1) * sizeof(int64_t)));
+  HIPC(hipMalloc(&T.col, ne * sizeof(int32_t)));
+  HIPC(hipMalloc(&T.val, ne * sizeof(double)));
+  HIPC(hipMemcpy(S.rowptr, rp.data(), (rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if (nnz) {
+    HIPC(hipMemcpy(S.col, ci.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(S.val, val, nnz * sizeof(double), hipMemcpyHostToDevice));
+  }
+  // the other orientation on the device (count, scan, fill, per-row sort: spmm_rect.hip)
+  const int te = rect_transpose(rows, ids, nnz, S.rowptr, S.col, S.val, T.rowptr, T.col, T.val, ctx->stream);
+  if (te != 0)
+    return fail(ctx, te == (int)hipErrorOutOfMemory ? RBL_ERR_OOM : RBL_ERR_HIP,
+                std::string("rbl_set_matrix_normal: device transpose: ") + hipGetErrorString((hipError_t)te));
+  std::vector<int64_t> tp(ids + 1);
+  HIPC(hipMemcpy(tp.data(), T.rowptr, (ids + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (tp[ids] != nnz) return fail(ctx, RBL_ERR_HIP, "rbl_set_matrix_normal: device transpose lost entries");
+  // the task tables of both orientations (64 doubles of scratch per segment slot: b <= 64 per launch)
+  CHK(build_seg(ctx, rp, S, kRectSegLen, kRectPack, kWave));
+  CHK(build_seg(ctx, tp, T, kRectSegLen, kRectPack, kWave));
+  ctx->need_lo.assign(1, 0);
+  ctx->need_hi.assign(1, 0);
+  return setup_halo(ctx);
+}
+
+int rbl_rect_info(rbl_ctx* ctx, int64_t* nrows, int64_t* ncols, int64_t* nnz) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (!ctx->rect) return fail(ctx, RBL_ERR_STATE, "rbl_rect_info: no rectangular matrix");
+  if (nrows) *nrows = ctx->rect_m;
+  if (ncols) *ncols = ctx->n;
+  if (nnz) *nnz = ctx->nnz;
+  return RBL_OK;
+}
+
+int rbl_get_matrix_rect(rbl_ctx* ctx, int trans, int64_t* rowptr, int32_t* colind, double* val) {
+  if (!ctx || (trans != 0 && trans != 1)) return fail(ctx, RBL_ERR_INVALID, "rbl_get_matrix_rect: bad arguments");
+  if (!ctx->rect) return fail(ctx, RBL_ERR_STATE, "rbl_get_matrix_rect: no rectangular matrix");
+  HIPC(hipSetDevice(ctx->device));
+  const auto& T = ctx->rect_side[trans];
+  const int64_t rows = trans ? ctx->n : ctx->rect_m;
+  if (rowptr) HIPC(hipMemcpy(rowptr, T.rowptr, (rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (colind && ctx->nnz)
+    HIPC(hipMemcpy(colind, T.col, ctx->nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (val && ctx->nnz) HIPC(hipMemcpy(val, T.val, ctx->nnz * sizeof(double), hipMemcpyDeviceToHost));
+  return RBL_OK;
+}
+
+namespace {
+// Y (rows of side `trans`) = side X (* scale per column), host column-major blocks of w columns
+static int rect_apply_host(rbl_ctx* ctx, int trans, int w, const double* X, double* Y, const double* scale) {
+  const int64_t rin = trans ? ctx->rect_m : ctx->n, rout = trans ? ctx->n : ctx->rect_m;
+  DevBuf x, xr, y, sc;
+  const int64_t rmax = std::max(rin, rout);
+  HIPC(hipMalloc(&x.p, rmax * w * sizeof(double)));
+  HIPC(hipMalloc(&xr.p, rin * w * sizeof(double)));
+  HIPC(hipMalloc(&y.p, rout * w * sizeof(double)));
+  if (scale) {
+    HIPC(hipMalloc(&sc.p, w * sizeof(double)));
+    HIPC(hipMemcpyAsync(sc.p, scale, w * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIPC(hipMemcpyAsync(x.p, X, rin * w * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  colmajor_to_rowmajor(x.d(), rin, w, xr.d(), ctx->stream);
+  {
+    StageScope t(ctx, RBL_STAGE_AQ);
+    spmm_rect(rect_tier(ctx, trans), xr.d(), w, y.d(), nullptr, nullptr, sc.d(), ctx->stream);
+  }
+  HIPC(hipGetLastError());
+  rowmajor_to_colmajor(y.d(), rout, w, x.d(), ctx->stream);
+  HIPC(hipMemcpyAsync(Y, x.p, rout * w * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  harvest_timers(ctx);
+  return RBL_OK;
+}
+}  // namespace
+
+int rbl_apply_rect(rbl_ctx* ctx, int trans, int b, const double* X, double* Y) {
+  if (!ctx || (trans != 0 && trans != 1) || b < 1 || b > RBL_MAX_BLOCK || !X || !Y)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_apply_rect: bad arguments");
+  if (!ctx->rect) return fail(ctx, RBL_ERR_STATE, "rbl_apply_rect: no rectangular matrix");
+  HIPC(hipSetDevice(ctx->device));
+  return rect_apply_host(ctx, trans, b, X, Y, nullptr);
+}
+
+int rbl_left_vectors(rbl_ctx* ctx, int k, const double* V, const double* sigma, double* U_out) {
+  if (!ctx || k < 1 || k > RBL_MAX_BLOCK || !V || !sigma || !U_out)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_left_vectors: bad arguments");
+  if (!ctx->rect) return fail(ctx, RBL_ERR_STATE, "rbl_left_vectors: no rectangular matrix");
+  HIPC(hipSetDevice(ctx->device));
+  std::vector<double> inv(k);
+  for (int j = 0; j < k; ++j) inv[j] = 1.0 / sigma[j];  // U = (B V) ./ transpose(D), images.jl:24
+  return rect_apply_host(ctx, 0, k, V, U_out, inv.data());
+}
+
 int rbl_matrix_info(rbl_ctx* ctx, int64_t* n, int64_t* row_begin, int64_t* row_end,
                     int64_t* nnz_local) {
   if (!ctx) return RBL_ERR_INVALID;
@@ -2827,7 +3022,9 @@ int rbl_get_matrix_csr(rbl_ctx* ctx, int64_t* rowptr, int32_t* colind, double* v
   if (ctx && ctx->csr_dropped)
     return fail(ctx, RBL_ERR_STATE, "rbl_get_matrix_csr: the CSR was released (RBL_OPT_KEEP_CSR = 0)");
   if (!ctx || !ctx->d_rowptr)
-    return fail(ctx, RBL_ERR_STATE, ctx && ctx->dense ? "dense matrix: no CSR" : "no matrix");
+    return fail(ctx, RBL_ERR_STATE, ctx && ctx->dense  ? "dense matrix: no CSR"
+                                    : ctx && ctx->rect ? "rectangular matrix: use rbl_get_matrix_rect"
+                                                       : "no matrix");
   HIPC(hipSetDevice(ctx->device));
   if (rowptr)
     HIPC(hipMemcpy(rowptr, ctx->d_rowptr, (ctx->nloc + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -2841,6 +3038,7 @@ int rbl_get_matrix_csr(rbl_ctx* ctx, int64_t* rowptr, int32_t* colind, double* v
 int rbl_spmm_kernel_for(rbl_ctx* ctx, int b) {
   if (!ctx || !has_matrix(ctx)) return RBL_ERR_INVALID;
   if (ctx->dense) return 4;
+  if (ctx->rect) return 8;
   if (ctx->spmm_variant == 1) return 1;
   const int v = ctx->spmm_variant;
   const bool band = ctx->ntiles > 0 && ((b == 16 && ctx->band_ok16) || (b == 32 && ctx->band_ok32));
@@ -2857,6 +3055,7 @@ int rbl_spmm_kernel_for(rbl_ctx* ctx, int b) {
 int rbl_matrix_format(rbl_ctx* ctx) {
   if (!ctx || !has_matrix(ctx)) return RBL_ERR_INVALID;
   if (ctx->dense) return 4;
+  if (ctx->rect) return 5;
   if (ctx->d_bth) return 3;
   if (ctx->d_btp_hdr) return 2;
   if (ctx->d_bt) return 1;
@@ -2922,6 +3121,9 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   if (max_blocks < 1) return fail(ctx, RBL_ERR_INVALID, "max_blocks must be >= 1");
   if (basis_bits != 64 && basis_bits != 32)
     return fail(ctx, RBL_ERR_INVALID, "basis_bits must be 64 or 32");
+  if (ctx->rect && basis_bits != 64)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_start: a rectangular B (rbl_set_matrix_normal) needs the "
+                                      "fp64 basis (basis_bits = 64)");
   HIPC(hipSetDevice(ctx->device));
   HIPC(hipStreamSynchronize(ctx->stream));
   // a repeated run with the same shape reuses the HBM plan (allocating ~100 GB of basis

@@ -45,6 +45,9 @@ RBL_PATH_SPMM_TWO_WAVE = 6
 RBL_PATH_RITZ_PIECES = 7
 RBL_PATH_NSTATS = 8
 RBL_BUILD_VARIANTS = 1
+# a rectangular B (rbl_set_matrix_normal): what rbl_spmm_kernel_for / rbl_matrix_format report
+RBL_SPMM_KERNEL_RECT = 8
+RBL_MATRIX_FORMAT_RECT = 5
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -74,6 +77,11 @@ SIGNATURES = {
     "rbl_set_matrix_csc": (C.c_int, [_p, _i64, _i64, _pi64, _pi64, _pd, C.c_int]),
     "rbl_set_matrix_csr_rows": (C.c_int, [_p, _i64, _i64, _i64, _pi64, _pi64, _pd, C.c_int]),
     "rbl_set_matrix_dense": (C.c_int, [_p, _i64, _i64, _i64, _pd, _i64]),
+    "rbl_set_matrix_normal": (C.c_int, [_p, _i64, _i64, _i64, _pi64, _pi64, _pd, C.c_int, C.c_int]),
+    "rbl_rect_info": (C.c_int, [_p, _pi64, _pi64, _pi64]),
+    "rbl_get_matrix_rect": (C.c_int, [_p, C.c_int, _pi64, _pi32, _pd]),
+    "rbl_apply_rect": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd]),
+    "rbl_left_vectors": (C.c_int, [_p, C.c_int, _pd, _pd, _pd]),
     "rbl_gen_matrix_hashwindow": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_circuit": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_rmat": (C.c_int, [_p, _i64, C.c_int, _i64, C.c_double, C.c_double, C.c_double,

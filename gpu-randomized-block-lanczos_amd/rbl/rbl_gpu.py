@@ -153,6 +153,69 @@ class Context:
                                                 i64ptr(colind), dptr(val), index_base),
                     "rbl_set_matrix_csr_rows")
 
+    # -- rectangular sparse B: the implicit normal operator B^T B ----------------------------
+    def set_matrix_normal(self, B) -> None:
+        """Upload a rectangular sparse B (m x n, any SciPy sparse format) for its singular
+        triplets (rbl_set_matrix_normal): the Krylov operator is B^T B, applied as B^T (B Q) and
+        never formed.  CSR arrays go over as they stand with layout 0, CSC arrays with layout 1
+        (other formats are converted to CSR); the other orientation is built on the device.
+        One rank, fp64 basis."""
+        if not sp.issparse(B) or B.ndim != 2:
+            raise ValueError("set_matrix_normal: B must be a 2-D SciPy sparse matrix")
+        if B.format not in ("csr", "csc"):
+            B = B.tocsr()
+        if not B.has_canonical_format:      # sorted, no duplicates (a copy: B is the caller's)
+            B = B.copy()
+            B.sum_duplicates()
+        m, n = B.shape
+        ptr = np.ascontiguousarray(B.indptr, dtype=np.int64)
+        ind = np.ascontiguousarray(B.indices, dtype=np.int64)
+        val = np.ascontiguousarray(B.data, dtype=np.float64)
+        self._check(lib.rbl_set_matrix_normal(self._h, m, n, B.nnz, i64ptr(ptr), i64ptr(ind),
+                                              dptr(val), 0, 0 if B.format == "csr" else 1),
+                    "rbl_set_matrix_normal")
+
+    def rect_info(self):
+        """(m, n, nnz) of the rectangular B held (rbl_rect_info)."""
+        v = [np.zeros(1, np.int64) for _ in range(3)]
+        self._check(lib.rbl_rect_info(self._h, *[i64ptr(x) for x in v]), "rbl_rect_info")
+        return tuple(int(x[0]) for x in v)
+
+    def get_matrix_rect(self, trans: bool = False):
+        """One device orientation as (rowptr, ind, val), 0-based: B's CSR, or with trans B^T's."""
+        m, n, nnz = self.rect_info()
+        rows = n if trans else m
+        rowptr = np.zeros(rows + 1, np.int64)
+        ind = np.zeros(max(nnz, 1), np.int32)
+        val = np.zeros(max(nnz, 1), np.float64)
+        self._check(lib.rbl_get_matrix_rect(self._h, int(bool(trans)), i64ptr(rowptr), i32ptr(ind),
+                                            dptr(val)), "rbl_get_matrix_rect")
+        return rowptr, ind[:nnz], val[:nnz]
+
+    def apply_rect(self, X: np.ndarray, trans: bool = False) -> np.ndarray:
+        """Y = B X (X: n x b), or with trans Y = B^T X (X: m x b): one pass of the gather pair."""
+        m, n, _ = self.rect_info()
+        rin, rout = (m, n) if trans else (n, m)
+        X = np.asfortranarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] != rin:
+            raise ValueError(f"apply_rect: X must have {rin} rows")
+        Y = np.zeros((rout, X.shape[1]), order="F")
+        self._check(lib.rbl_apply_rect(self._h, int(bool(trans)), X.shape[1], dptr(X), dptr(Y)),
+                    "rbl_apply_rect")
+        return Y
+
+    def left_vectors(self, V: np.ndarray, sigma) -> np.ndarray:
+        """U = B V diag(1 / sigma) (images.jl:24), m x k, from V (n x k) and the singular values."""
+        m, n, _ = self.rect_info()
+        V = np.asfortranarray(V, dtype=np.float64)
+        sigma = np.ascontiguousarray(sigma, dtype=np.float64).ravel()
+        if V.ndim != 2 or V.shape[0] != n or sigma.size != V.shape[1]:
+            raise ValueError("left_vectors: V must be n x k and sigma of length k")
+        U = np.zeros((m, V.shape[1]), order="F")
+        self._check(lib.rbl_left_vectors(self._h, V.shape[1], dptr(V), dptr(sigma), dptr(U)),
+                    "rbl_left_vectors")
+        return U
+
     def gen_hashwindow(self, n: int, halfwidth: int, density: float, seed: int,
                        plant=None) -> None:
         plant = np.ascontiguousarray(plant if plant is not None else np.zeros(0), np.float64)
@@ -210,13 +273,14 @@ class Context:
         return Y
 
     def matrix_format(self) -> int:
-        """0 CSR only, 1 band tiles, 2 packed band tiles, 3 half band tiles, 4 dense."""
+        """0 CSR only, 1 band tiles, 2 packed band tiles, 3 half band tiles, 4 dense,
+        5 rectangular B (both orientations as CSR)."""
         return self._check(lib.rbl_matrix_format(self._h), "rbl_matrix_format")
 
     def spmm_kernel_for(self, b: int) -> int:
         """The SpMM kernel rbl_step runs at block size b: 1 global-gather CSR, 2 LDS-window CSR,
-        3 LDS-densified band, 4 dense panels, 5 band tiles, 6 segmented gather (the same ids
-        RBL_OPT_SPMM_KERNEL takes)."""
+        3 LDS-densified band, 4 dense panels, 5 band tiles, 6 segmented gather, 7 column panels
+        (the same ids RBL_OPT_SPMM_KERNEL takes), 8 the rectangular gather pair."""
         return self._check(lib.rbl_spmm_kernel_for(self._h, b), "rbl_spmm_kernel_for")
 
     # -- Krylov run -------------------------------------------------------------------------

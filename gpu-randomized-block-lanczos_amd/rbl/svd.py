@@ -1,0 +1,53 @@
+"""Truncated SVD of a rectangular sparse B by randomized block Lanczos on the implicit normal
+operator B^T B — the third use of the reference (images.jl:20-33):
+
+    D, V = RBL_gpu(transpose(B) * B, k, 1)     # images.jl:29
+    D = sqrt.(D)                                # :23
+    U = (B * V) ./ transpose(D)                 # :24
+
+Here B^T B is never formed: the device holds B and B^T as CSR (rbl_set_matrix_normal) and a block
+step applies B^T (B Q_i) in two gather passes.  The loop, its convergence test (on the eigenvalues
+sigma^2) and the Ritz projection are those of ``RBL_gpu``.
+"""
+from __future__ import annotations
+
+import numpy as np
+import scipy.sparse as sp
+
+from .rbl_gpu import KRYL_SZ_GPU, Context, lanczos
+
+
+def _validate(B, k, side):
+    if not sp.issparse(B) or B.ndim != 2:
+        raise ValueError("RBL_svd: B must be a 2-D SciPy sparse matrix")
+    m, n = B.shape
+    if not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError("RBL_svd: k must be an integer >= 1")
+    if k > min(m, n):
+        raise ValueError(f"RBL_svd: k = {k} exceeds min(m, n) = {min(m, n)}")
+    if side not in ("auto", "right", "left"):
+        raise ValueError("RBL_svd: side must be 'auto', 'right' or 'left'")
+    return m, n
+
+
+def RBL_svd(B, k: int, b: int, *, side: str = "auto", omega=None, seed: int = 0,
+            kryl_sz: int = KRYL_SZ_GPU, return_info: bool = False, device: int = 0):
+    """The k largest singular triplets of B (m x n): returns (U, S, V) with S descending,
+    U m x k, V n x k, B V = U diag(S).
+
+    side: the dimension the Krylov basis lives on — "right" iterates on B^T B (n rows: V are the
+    Ritz vectors, U = B V / S), "left" on B B^T (m rows, by setting B^T — free through the layout
+    flag — and swapping U and V at the end), "auto" the smaller of the two.  omega: the start
+    block (rows of the iterated dimension) instead of the seeded device draw."""
+    m, n = _validate(B, k, side)
+    if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b < 1:
+        raise ValueError("RBL_svd: b must be an integer >= 1")
+    left = side == "left" or (side == "auto" and m < n)
+    with Context(device) as ctx:
+        ctx.set_matrix_normal(B.T if left else B)   # CSR <-> CSC views: no host conversion
+        D, V, info = lanczos(ctx, k, b, kryl_sz=kryl_sz, omega=omega, seed=seed)
+        S = np.sqrt(np.maximum(D, 0.0))
+        U = ctx.left_vectors(V, S)
+    if left:
+        U, V = V, U
+    return (U, S, V, info) if return_info else (U, S, V)

@@ -81,7 +81,9 @@ extern "C" {
                                    * read >= 4 times, i.e. bands wider than the band tiles' 64).
                                    * Each falls back 5 -> 3 -> 2 -> 1 (7 -> 1) when the matrix
                                    * does not fit the kernel's limits.  4 (dense panels) follows
-                                   * from rbl_set_matrix_dense and is rejected here.           */
+                                   * from rbl_set_matrix_dense and is rejected here.  With a
+                                   * rectangular B (rbl_set_matrix_normal) every value falls back
+                                   * to 8, the rectangular gather pair.                        */
 #define RBL_OPT_SPLIT_HALO    4   /* several ranks, band-tile SpMM: 1 (default) the kernel reads
                                    * the own rows from the block and the halo buffer holds only
                                    * the neighbours' rows; 0 the own block is copied into the
@@ -215,6 +217,41 @@ int rbl_set_matrix_dense(rbl_ctx* ctx, int64_t n, int64_t row_begin, int64_t row
  * entry (r,c), |r-c| <= halfwidth, r != c, exists iff hash(seed,min,max) < density, with a
  * uniform(-1,1) value from the same hash; diagonal = uniform(-1,1) plus plant[l] at row
  * l*floor(n/nplant) for l < nplant.  Each rank generates only its own rows. */
+/* Rectangular sparse B (nrows x ncols) for its k largest singular triplets (images.jl:20-33 runs
+ * RBL_gpu(transpose(B)*B, k, 1) and recovers U = (B*V) ./ transpose(D)): the Krylov operator is
+ * B^T B (ncols x ncols), applied as B^T (B Q) and never formed.
+ *   layout 0: ptr / ind are B's CSR (ptr: nrows + 1, ind: column ids);
+ *   layout 1: B's CSC (ptr: ncols + 1, ind: row ids) — Julia's SparseMatrixCSC as it is
+ *             (index_base 1).  Passing B's CSR with layout 1 and the sizes swapped sets B^T.
+ * Indices strictly ascending within each row (layout 0) / column (layout 1): sorted, no
+ * duplicates.  The device holds both orientations (int32 ids, int64 row pointers: 2 x 12 B per
+ * nonzero + (nrows + ncols + 2) x 8 B, and an nrows x b fp64 work block); the orientation not
+ * passed is built on the device, every row ascending in the other index — the same arrays on
+ * every run.  nrows, ncols < 2^31 and nnz < 2^31 - 1, else RBL_ERR_INVALID.
+ * Afterwards: rbl_matrix_info reports n = ncols, rows [0, ncols), nnz_local = nnz; rbl_apply
+ * computes B^T B X; rbl_start / rbl_step / rbl_ritz run on B^T B (eigenvalues sigma^2, Ritz
+ * vectors = right singular vectors); rbl_spmm_kernel_for reports 8 for every b and
+ * rbl_matrix_format 5; rbl_get_matrix_csr fails (RBL_ERR_STATE, as for a dense A);
+ * RBL_OPT_KEEP_CSR has no effect and a forced RBL_OPT_SPMM_KERNEL falls back to kernel 8.
+ * Limits: one rank only — on a context with nranks > 1 this returns RBL_ERR_INVALID before any
+ * collective; the fp64 basis only — rbl_start with basis_bits = 32 returns RBL_ERR_INVALID. */
+#define RBL_SPMM_KERNEL_RECT   8   /* rbl_spmm_kernel_for with a rectangular B */
+#define RBL_MATRIX_FORMAT_RECT 5   /* rbl_matrix_format with a rectangular B   */
+int rbl_set_matrix_normal(rbl_ctx* ctx, int64_t nrows, int64_t ncols, int64_t nnz,
+                          const int64_t* ptr, const int64_t* ind, const double* val,
+                          int index_base, int layout);
+/* Shape of the rectangular B held (RBL_ERR_STATE when the matrix is of another kind). */
+int rbl_rect_info(rbl_ctx* ctx, int64_t* nrows, int64_t* ncols, int64_t* nnz);
+/* Download one orientation (trans 0: B's CSR, nrows + 1 pointers; 1: B^T's CSR, ncols + 1),
+ * 0-based — test/inspection only. */
+int rbl_get_matrix_rect(rbl_ctx* ctx, int trans, int64_t* rowptr, int32_t* colind, double* val);
+/* One pass of the pair, host column-major blocks: trans 0: Y (nrows x b) = B X (ncols x b);
+ * trans 1: Y (ncols x b) = B^T X (nrows x b).  Timed under "AQ" while RBL_OPT_TIMERS is set. */
+int rbl_apply_rect(rbl_ctx* ctx, int trans, int b, const double* X, double* Y);
+/* Left singular vectors U_out (nrows x k, column-major) = B V diag(1 / sigma) — images.jl:24,
+ * `U = (B*V) ./ transpose(D)` — from V (ncols x k, column-major) and the k singular values:
+ * pass 1 of the pair with the per-column scale in its epilogue.  k <= RBL_MAX_BLOCK. */
+int rbl_left_vectors(rbl_ctx* ctx, int k, const double* V, const double* sigma, double* U_out);
 int rbl_gen_matrix_hashwindow(rbl_ctx* ctx, int64_t n, int64_t halfwidth, double density,
                               uint64_t seed, int nplant, const double* plant);
 /* Device-side generator of the seeded symmetric R-MAT matrix (BASELINE
@@ -249,12 +286,14 @@ int rbl_apply(rbl_ctx* ctx, int b, const double* X, double* Y);
 /* Which SpMM kernel rbl_step / rbl_apply use for block size b under the current option:
  * 1 = global-gather CSR, 2 = LDS-window CSR (DPP), 3 = LDS-densified band on fp64 MFMA,
  * 4 = dense panel GEMM (rbl_set_matrix_dense), 5 = band-tile format on fp64 MFMA,
- * 6 = segmented gather (unstructured patterns, b in {16, 32}). */
+ * 6 = segmented gather (unstructured patterns, b in {16, 32}), 7 = column panels,
+ * 8 = rectangular gather pair (rbl_set_matrix_normal, every b). */
 int rbl_spmm_kernel_for(rbl_ctx* ctx, int b);
 /* The device format the matrix is held in: 0 = CSR only, 1 = band tiles (16 x (16 + 2H)
  * doubles), 2 = packed band tiles (RBL_BT_PACK=1), 3 = half band tiles (A symmetric bit for
  * bit: diagonal block + right strip, the left part transposed back in the kernel, same
- * results as 1; opt-in with RBL_BT_HALF=1), 4 = dense panels. */
+ * results as 1; opt-in with RBL_BT_HALF=1), 4 = dense panels, 5 = rectangular B as two CSRs
+ * (B and B^T, rbl_set_matrix_normal). */
 int rbl_matrix_format(rbl_ctx* ctx);
 
 /* ---- Krylov run -----------------------------------------------------------------------

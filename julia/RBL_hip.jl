@@ -14,6 +14,7 @@
 #   D, V = RBL_hip(A, k, b; basis_bits = 32)      # FLOAT = Float32 mode (common.jl:5)
 #   D, V = RBL_hip(A, k, b; device_blocks = -1)   # hybrid buffer: what fits in HBM, rest on host
 #   D, V = RBL_hip_restarted(A, k)       # restarted.jl:106 (RBL_gpu_restarted)
+#   U, D, V = RBL_gpu_svd(B, k, b)       # images.jl:29-33 on a sparse rectangular B, B^T B implicit
 #
 # Untested here: Julia is not installed in the build container (SURVEY §8(c)).  Every ccall
 # below is checked against include/rbl_hip.h by tests/test_julia_binding.py (argument count
@@ -60,6 +61,18 @@ set_matrix!(ctx, A::Matrix{Float64}) =
                          (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Int64),
                          ctx, size(A, 2), 0, size(A, 1), A, size(A, 1)), "rbl_set_matrix_dense")
 
+# A rectangular sparse B for its singular triplets: the SparseMatrixCSC arrays as they are
+# (layout 1 = B's CSC, 1-based); the device builds the other orientation and applies B^T (B Q).
+function set_matrix_normal!(ctx, B::SparseMatrixCSC{Float64})
+    colptr = Vector{Int64}(B.colptr)
+    rowval = Vector{Int64}(B.rowval)
+    rbl_check(ctx, ccall((:rbl_set_matrix_normal, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64},
+                          Cint, Cint),
+                         ctx, size(B, 1), size(B, 2), nnz(B), colptr, rowval, B.nzval, Cint(1),
+                         Cint(1)), "rbl_set_matrix_normal")
+end
+
 function rbl_context(device::Int)
     hr = Ref{Ptr{Cvoid}}(C_NULL)
     st = ccall((:rbl_create, librbl_hip), Cint, (Ref{Ptr{Cvoid}}, Cint), hr, Cint(device))
@@ -95,11 +108,13 @@ end
 function RBL_hip(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k::Int64, b::Int64;
                  device::Int = 0, seed::UInt64 = rand(UInt64), kryl_sz::Int64 = 1200,
                  basis_bits::Int = (FLOAT == Float32 ? 32 : 64), device_blocks::Int = 0,
-                 timer = nothing)
+                 timer = nothing, normal::Bool = false)
+    # normal: A is a rectangular B and the operator B^T B (RBL_gpu_svd); then the left singular
+    # vectors are formed before the context is released and returned as a third value
     n = size(A, 2)
     ctx = rbl_context(device)
     try
-        set_matrix!(ctx, A)
+        normal ? set_matrix_normal!(ctx, A) : set_matrix!(ctx, A)
         # RBL_OPT_DEVICE_BLOCKS: the hybrid GPU/host Krylov buffer (RBL_gpu.jl:24-27, 59-81)
         rbl_check(ctx, ccall((:rbl_set_option, librbl_hip), Cint, (Ptr{Cvoid}, Cint, Int64),
                              ctx, RBL_OPT_DEVICE_BLOCKS, device_blocks), "rbl_set_option")
@@ -202,6 +217,15 @@ function RBL_hip(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k::Int64, b
                       "rbl_synchronize")
             fold_device_timers!(timer, ctx)
         end
+        if normal
+            sigma = sqrt.(max.(D, 0.0))                             # images.jl:23
+            U = zeros(Float64, size(A, 1), k)
+            # U = (B*V) ./ transpose(D) (images.jl:24) on the device
+            rbl_check(ctx, ccall((:rbl_left_vectors, librbl_hip), Cint,
+                                 (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                 ctx, Cint(k), Vout, sigma, U), "rbl_left_vectors")
+            return sigma, Vout, U
+        end
         return D, Vout
     finally
         ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
@@ -215,6 +239,15 @@ end
 function RBL_gpu(A::Union{SparseMatrixCSC{DOUBLE},Matrix{DOUBLE}}, k::Int64, b::Int64)
     timer = isdefined(Main, :to) ? Main.to : nothing
     return RBL_hip(A, k, b; timer = timer)
+end
+
+# Drop-in for images.jl:29-33 on a sparse rectangular B: `D, V = RBL_gpu(transpose(B)*B, k, b)`,
+# `D = sqrt.(D)`, `U = (B*V) ./ transpose(D)` — without forming B^T B (rbl_set_matrix_normal).
+# Returns U (m x k), the singular values D (descending) and V (n x k).  The fp64 basis only.
+function RBL_gpu_svd(B::SparseMatrixCSC{DOUBLE}, k::Int64, b::Int64)
+    timer = isdefined(Main, :to) ? Main.to : nothing
+    D, V, U = RBL_hip(B, k, b; timer = timer, normal = true, basis_bits = 64)
+    return U, D, V
 end
 
 # restarted.jl:106-146 (RBL_gpu_restarted): b = 1 cycles with locking.  The cycle
