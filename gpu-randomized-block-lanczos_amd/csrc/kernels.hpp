@@ -292,6 +292,22 @@ constexpr int kBandRing = 256;
 // positions of every nonzero in its tile's dense band (CsrDev::band_pos), from tile_info
 void band_positions(const CsrDev& A, uint16_t* pos, hipStream_t s);
 
+// --- spmm_cheb.hip: row passes of the Chebyshev-filtered operator and of Rayleigh-Ritz on A --
+// out = alpha W + beta Y (+ gamma Z if Z) over `len` contiguous doubles (an n x b row-major
+// block): one term of the filter recurrence after its SpMM.  out may be W.  Any len >= 0; 16-byte
+// accesses when every pointer is 16-byte aligned; the grid follows the CU count.
+void cheb_axpby(int64_t len, const double* W, const double* Y, const double* Z, double alpha,
+                double beta, double gamma, double* out, hipStream_t s);
+// part[g][c] = sum over workgroup g's rows of (Z[r][c] - X[r][c] theta[c])^2, c < kp (Z, X: n x kp
+// row-major), g < grid = resid_grid(nrows): a fixed summation order, no atomics; reduce_slab
+// over the grid gives the squared column norms.
+int resid_grid(int64_t nrows);
+void resid_partial(int64_t nrows, int kp, const double* Z, const double* X, const double* theta,
+                   double* part, int grid, hipStream_t s);
+// dst[r][d0 + c] = src[r][s0 + c], c < w (row-major, leading dimensions ldd / lds)
+void copy_cols(int64_t nrows, int w, const double* src, int lds, int s0, double* dst, int ldd, int d0,
+               hipStream_t s);
+
 // --- tsmm.hip ----------------------------------------------------------------------------
 // Partial Gram:  slab[s][a][c] = sum over rows of split s of W[r][a] * X[r][c]
 //   W: run of nW panels (a in [0, nW*w)), X: panels (c in [0, X.count*X.w)).

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -207,6 +208,18 @@ struct rbl_ctx {
   // vector j at d_lock + j * nloc (a width-1 panel)
   double* d_lock = nullptr;
   int nlock = 0, lock_cap = 0;
+  // Chebyshev filter (rbl_set_filter; degree 0: none): the Krylov operator is p(A), applied by a
+  // three-term recurrence through two work blocks beside U, each (n_local + kRowPad) x filt_cols
+  // and zeroed like every block an SpMM writes; sized at rbl_start
+  int filt_deg = 0;
+  double filt_lo = 0.0, filt_hi = 0.0, filt_ref = 0.0;
+  double* d_filt[2] = {nullptr, nullptr};
+  int filt_cols = 0;
+  // Rayleigh-Ritz on A between rbl_ritz_project and rbl_ritz_finish: V = [Q_1..Q_m] S and
+  // W = A V, (n_local + kRowPad) x ritz_kp row-major (ritz_kp = ritz_k rounded up to even)
+  double* d_rv = nullptr;
+  double* d_rw = nullptr;
+  int ritz_k = 0;
 
   // options
   int timers = 0;  // RBL_OPT_TIMERS: 0 off, 1 every stage, 2 the SpMM and partial-reorth stages
@@ -1616,6 +1629,68 @@ int apply_A(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* U, cons
   return 0;
 }
 
+// The two work blocks of the filter recurrence for block size b (allocated and zeroed like d_U:
+// the band kernels store unguarded into the kRowPad spare rows).
+int ensure_filter_bufs(rbl_ctx* ctx, int b) {
+  if (ctx->d_filt[0] && ctx->d_filt[1] && ctx->filt_cols >= b) return RBL_OK;
+  HIPC(hipStreamSynchronize(ctx->stream));
+  const size_t bytes = (size_t)(std::max<int64_t>(ctx->nloc, 1) + kRowPad) * b * sizeof(double);
+  for (double*& p : ctx->d_filt) {
+    hipFree(p);
+    p = nullptr;
+  }
+  ctx->filt_cols = 0;
+  for (double*& p : ctx->d_filt) {
+    HIPC(hipMalloc(&p, bytes));
+    HIPC(hipMemsetAsync(p, 0, bytes, ctx->stream));
+  }
+  ctx->filt_cols = b;
+  return RBL_OK;
+}
+
+// Per-term scalars of the scaled Chebyshev recurrence (Zhou & Saad): Y_j = al A Y_{j-1} +
+// be Y_{j-1} + ga Y_{j-2} (rbl.filtered.cheb_scalars is the same arithmetic on the host).
+struct ChebTerm { double al, be, ga; };
+std::vector<ChebTerm> cheb_terms(int degree, double lo, double hi, double ref) {
+  const double c = 0.5 * (lo + hi), e = 0.5 * (hi - lo);
+  const double s1 = e / (ref - c);
+  std::vector<ChebTerm> t;
+  t.push_back({s1 / e, -(s1 / e) * c, 0.0});
+  double sg = s1;
+  for (int j = 2; j <= degree; ++j) {
+    const double sn = 1.0 / (2.0 / s1 - sg);
+    t.push_back({2.0 * sn / e, -(2.0 * sn / e) * c, -sg * sn});
+    sg = sn;
+  }
+  return t;
+}
+
+// out = p(A) X (rbl_set_filter), one rank: X, out and the work blocks F0, F1 are distinct
+// n_local x b row-major blocks; out, F0, F1 carry the kRowPad spare rows.  X is only read.
+// Term j's SpMM writes W = A Y_{j-1} into the block that held Y_{j-3} (dead by then), and the
+// row pass turns it into Y_j in place; the rotation starts so that Y_degree lands in `out`.
+int cheb_apply(rbl_ctx* ctx, const double* X, int b, double* out, double* F0, double* F1) {
+  if (ctx->nloc <= 0) return RBL_OK;
+  const std::vector<ChebTerm> terms = cheb_terms(ctx->filt_deg, ctx->filt_lo, ctx->filt_hi, ctx->filt_ref);
+  double* buf[3] = {out, F0, F1};
+  const int d = ctx->filt_deg;
+  const int shift = (3 - d % 3) % 3;  // Y_j lives in buf[(j + shift) % 3]; Y_d in buf[0]
+  const double* y1 = X;        // Y_{j-1}
+  const double* y2 = nullptr;  // Y_{j-2}
+  const int64_t len = ctx->nloc * b;
+  for (int j = 1; j <= d; ++j) {
+    double* yj = buf[(j + shift) % 3];
+    const int st = apply_A(ctx, y1, 0, b, yj, nullptr, nullptr, nullptr);
+    if (st < 0) return st;
+    const ChebTerm& t = terms[j - 1];
+    cheb_axpby(len, yj, y1, j >= 2 ? y2 : nullptr, t.al, t.be, t.ga, yj, ctx->stream);
+    HIPC(hipGetLastError());
+    y2 = y1;
+    y1 = yj;
+  }
+  return RBL_OK;
+}
+
 // X -= l (l^T X) for every locked vector l in lock order (restarted.jl:1-21,
 // restart_reorth_gpu!: one projection per locked vector, MGS over them).
 int lock_reorth(rbl_ctx* ctx, double* X) {
@@ -2175,6 +2250,12 @@ void free_run(rbl_ctx* ctx) {
   hipFree(ctx->d_flags); ctx->d_flags = nullptr;
   hipFree(ctx->d_lock); ctx->d_lock = nullptr;
   ctx->nlock = ctx->lock_cap = 0;
+  hipFree(ctx->d_filt[0]); hipFree(ctx->d_filt[1]);
+  ctx->d_filt[0] = ctx->d_filt[1] = nullptr;
+  ctx->filt_cols = 0;
+  hipFree(ctx->d_rv); ctx->d_rv = nullptr;
+  hipFree(ctx->d_rw); ctx->d_rw = nullptr;
+  ctx->ritz_k = 0;
   if (ctx->h_pin) hipHostFree(ctx->h_pin);
   ctx->h_pin = nullptr;
   if (ctx->h_hist) hipHostFree(ctx->h_hist);
@@ -3124,6 +3205,12 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   if (ctx->rect && basis_bits != 64)
     return fail(ctx, RBL_ERR_INVALID, "rbl_start: a rectangular B (rbl_set_matrix_normal) needs the "
                                       "fp64 basis (basis_bits = 64)");
+  if (ctx->filt_deg > 0 && basis_bits != 64)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_start: a Chebyshev filter (rbl_set_filter) needs the fp64 "
+                                      "basis (basis_bits = 64)");
+  if (ctx->filt_deg > 0 && (ctx->rect || ctx->nranks > 1))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_start: a Chebyshev filter (rbl_set_filter) runs on one rank "
+                                      "and a square A only");
   HIPC(hipSetDevice(ctx->device));
   HIPC(hipStreamSynchronize(ctx->stream));
   // a repeated run with the same shape reuses the HBM plan (allocating ~100 GB of basis
@@ -3267,6 +3354,7 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
       return fail(ctx, RBL_ERR_OOM, "rbl_start: push buffers (injected by RBL_FAULT_PUSH_ALLOC)");
     CHK(ensure_push(ctx, b));
   }
+  if (ctx->filt_deg > 0) CHK(ensure_filter_bufs(ctx, b));
   return RBL_OK;
   }();
   if (ctx->nranks > 1) {
@@ -3304,7 +3392,10 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   CHK(halo_exchange(ctx, ctx->d_T, &Qin, &off));
   {
     StageScope t(ctx, RBL_STAGE_AQ);
-    CHK(apply_A(ctx, Qin, off, b, ctx->d_U, nullptr, nullptr, nullptr));
+    if (ctx->filt_deg > 0)  // Q_1 = qr(p(A) Omega).Q
+      CHK(cheb_apply(ctx, ctx->d_T, b, ctx->d_U, ctx->d_filt[0], ctx->d_filt[1]));
+    else
+      CHK(apply_A(ctx, Qin, off, b, ctx->d_U, nullptr, nullptr, nullptr));
     HIPC(hipGetLastError());
   }
   CHK(push_halo(ctx, ctx->d_T, b, ctx->d_U));
@@ -3465,8 +3556,10 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
   ctx->step_flags[i] = part_reorth;
   // fuse bit 2: the update itself rides on the SpMM below, which stages Q_i's rows corrected
   // (fp64 basis, band tiles at b = 32; no collective depends on the choice)
+  // (not with a Chebyshev filter: the staging fusion assumes U = A Q_i from one SpMM)
+  const bool filt = ctx->filt_deg > 0;
   const bool lfuse = !f32 && i >= 2 && (ctx->fuse & 4) && fused && !ctx->dense && ctx->nloc > 0 &&
-                     rbl_spmm_kernel_for(ctx, b) == 5 && spmm_bt_locfix_ok(csr(ctx), b);
+                     !filt && rbl_spmm_kernel_for(ctx, b) == 5 && spmm_bt_locfix_ok(csr(ctx), b);
   const double* Cloc = nullptr;
   int64_t lf_lo = 0, lf_hi = ctx->nloc;
   if (!f32 && i >= 2) {
@@ -3500,7 +3593,22 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
   // U = A Q_i - Q_{i-1} B_i^T   (RBL_gpu.jl:176-177)
   int ai_parts = 0;
   bool pushed = false;  // the push/pull split's partials sent on the side stream
-  {
+  if (filt) {
+    // U = p(A) Q_i - Q_{i-1} B_i^T (one rank, fp64 basis): the recurrence reads Q_i and leaves
+    // it and Q_{i-1} as they are; no fused route of the plain step applies (no local-reorth
+    // staging, no A_i partials, no split source), A_i = Q_i^T U comes from the Gram below
+    if (f32 || ctx->nranks > 1 || ctx->rect)
+      return fail(ctx, RBL_ERR_INVALID, "rbl_step: a Chebyshev filter needs one rank, a square A and "
+                                        "the fp64 basis");
+    CHK(ensure_filter_bufs(ctx, b));
+    StageScope t(ctx, RBL_STAGE_AQ);
+    CHK(cheb_apply(ctx, Qi, b, ctx->d_U, ctx->d_filt[0], ctx->d_filt[1]));
+    if (i >= 2) {
+      transpose_small(smallp(ctx, S_BPREV), smallp(ctx, S_BT), b, ctx->stream);
+      CHK(tsmm_checked(ctx, run1(Qm, b), smallp(ctx, S_BT), b, pan1(ctx->d_U, b), -1.0, 1.0, nullptr));
+    }
+    HIPC(hipGetLastError());
+  } else {
     const double* Qin = nullptr;
     const float* Qin32 = nullptr;
     int64_t off = 0;
@@ -3895,6 +4003,200 @@ int rbl_ritz(rbl_ctx* ctx, int nblocks, int k, const double* S, double* V_out) {
   if (trace)
     fprintf(stderr, "rbl_ritz: alloc %.2f ms, S + combine + transpose %.2f ms, D2H %.2f ms, total %.2f ms\n",
             t_alloc, t_comp, t_d2h, tnow() - t0);
+  return RBL_OK;
+}
+
+// ---- Chebyshev-filtered runs ---------------------------------------------------------------
+int rbl_set_filter(rbl_ctx* ctx, int degree, double lo, double hi, double ref) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (degree < 0) return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter: degree must be >= 0");
+  if (degree == 0) {
+    ctx->filt_deg = 0;
+    return RBL_OK;
+  }
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !std::isfinite(ref))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter: lo, hi and ref must be finite");
+  if (!(lo < hi)) return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter: needs lo < hi");
+  if (ref >= lo && ref <= hi)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter: ref must lie outside the damped interval [lo, hi]");
+  if (ctx->nranks > 1)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter: one rank only (nranks > 1 is not supported)");
+  if (ctx->rect)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter: not with a rectangular B (rbl_set_matrix_normal)");
+  if (ctx->d_basis32)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter: the fp64 basis only (the current run has basis_bits = 32)");
+  ctx->filt_deg = degree;
+  ctx->filt_lo = lo;
+  ctx->filt_hi = hi;
+  ctx->filt_ref = ref;
+  ctx->cloc_step = 0;  // the operator changes: no Gram of an earlier step carries over
+  return RBL_OK;
+}
+
+int rbl_apply_filter(rbl_ctx* ctx, int b, const double* X, double* Y) {
+  if (!ctx || b < 1 || b > RBL_MAX_BLOCK || !X || !Y)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_apply_filter: bad arguments");
+  if (!has_matrix(ctx)) return fail(ctx, RBL_ERR_STATE, "rbl_apply_filter: no matrix");
+  if (ctx->filt_deg < 1) return fail(ctx, RBL_ERR_STATE, "rbl_apply_filter: no filter set (rbl_set_filter)");
+  if (ctx->nranks > 1 || ctx->rect)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_apply_filter: one rank and a square A only");
+  HIPC(hipSetDevice(ctx->device));
+  const int64_t nl = std::max<int64_t>(ctx->nloc, 1);
+  const size_t padded = (size_t)(nl + kRowPad) * b * sizeof(double);
+  DevBuf x, xr, y, f0, f1;
+  HIPC(hipMalloc(&x.p, nl * b * sizeof(double)));
+  HIPC(hipMalloc(&xr.p, nl * b * sizeof(double)));
+  for (DevBuf* p : {&y, &f0, &f1}) {
+    HIPC(hipMalloc(&p->p, padded));
+    HIPC(hipMemsetAsync(p->p, 0, padded, ctx->stream));
+  }
+  HIPC(hipMemcpyAsync(x.p, X, ctx->nloc * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  colmajor_to_rowmajor(x.d(), ctx->nloc, b, xr.d(), ctx->stream);
+  {
+    StageScope t(ctx, RBL_STAGE_AQ);
+    CHK(cheb_apply(ctx, xr.d(), b, y.d(), f0.d(), f1.d()));
+  }
+  HIPC(hipGetLastError());
+  rowmajor_to_colmajor(y.d(), ctx->nloc, b, x.d(), ctx->stream);
+  HIPC(hipMemcpyAsync(Y, x.p, ctx->nloc * b * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  harvest_timers(ctx);
+  return RBL_OK;
+}
+
+// ---- Rayleigh-Ritz on A -------------------------------------------------------------------
+int rbl_ritz_project(rbl_ctx* ctx, int nblocks, int k, const double* S, double* H_out) {
+  if (!ctx || nblocks < 1 || k < 1 || !S || !H_out)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_ritz_project: bad arguments");
+  if (k > RBL_MAX_BLOCK)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_ritz_project: k must be <= " + std::to_string(RBL_MAX_BLOCK));
+  if (ctx->nranks > 1) return fail(ctx, RBL_ERR_INVALID, "rbl_ritz_project: one rank only");
+  if (!ctx->d_basis && !ctx->d_basis32) return fail(ctx, RBL_ERR_STATE, "rbl_ritz_project before rbl_start");
+  if (nblocks > ctx->nblocks) return fail(ctx, RBL_ERR_INVALID, "rbl_ritz_project: more blocks than computed");
+  if (k > nblocks * ctx->b) return fail(ctx, RBL_ERR_INVALID, "rbl_ritz_project: k > nblocks*b");
+  HIPC(hipSetDevice(ctx->device));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  hipFree(ctx->d_rv);
+  hipFree(ctx->d_rw);
+  ctx->d_rv = ctx->d_rw = nullptr;
+  ctx->ritz_k = 0;
+  const int b = ctx->b;
+  const int kp = (k + 1) & ~1;  // even width (16-B row stores), the pad column zero
+  const int64_t rows = (int64_t)nblocks * b;
+  const int64_t nl = std::max<int64_t>(ctx->nloc, 1);
+  const size_t vbytes = (size_t)(nl + kRowPad) * kp * sizeof(double);
+  HIPC(hipMalloc(&ctx->d_rv, vbytes));
+  HIPC(hipMalloc(&ctx->d_rw, vbytes));
+  HIPC(hipMemsetAsync(ctx->d_rv, 0, vbytes, ctx->stream));
+  HIPC(hipMemsetAsync(ctx->d_rw, 0, vbytes, ctx->stream));
+  // V = [Q_1..Q_nblocks] S, kept on the device
+  std::vector<double> srm((size_t)rows * kp);
+  for (int64_t r = 0; r < rows; ++r)
+    for (int c = 0; c < kp; ++c) srm[(size_t)r * kp + c] = c < k ? S[(size_t)c * rows + r] : 0.0;
+  DevBuf dS;
+  HIPC(hipMalloc(&dS.p, rows * kp * sizeof(double)));
+  HIPC(hipMemcpyAsync(dS.p, srm.data(), rows * kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  {
+    StageScope t(ctx, RBL_STAGE_RITZ);
+    if (ctx->basis_bits == 64) CHK(combine_blocks(ctx, nblocks, kp, dS.d(), ctx->d_rv));
+    else CHK(combine_blocks32(ctx, nblocks, kp, dS.d(), ctx->d_rv));
+  }
+  // W = A V with the plain operator, in column chunks of the run's block size where that is
+  // one the MFMA SpMM kernels take (b in {16, 32}; the only widths left once the CSR is
+  // released), else all columns at once through the kernel rbl_spmm_kernel_for(kp) names
+  {
+    StageScope t(ctx, RBL_STAGE_AQ);
+    const int cw = (b == 16 || b == 32) ? b : kp;
+    if (cw == kp) {
+      const int st = apply_A(ctx, ctx->d_rv, 0, kp, ctx->d_rw, nullptr, nullptr, nullptr);
+      if (st < 0) return st;
+    } else {
+      const size_t cbytes = (size_t)(nl + kRowPad) * cw * sizeof(double);
+      DevBuf xc, yc;
+      HIPC(hipMalloc(&xc.p, cbytes));
+      HIPC(hipMalloc(&yc.p, cbytes));
+      HIPC(hipMemsetAsync(xc.p, 0, cbytes, ctx->stream));
+      HIPC(hipMemsetAsync(yc.p, 0, cbytes, ctx->stream));
+      for (int c0 = 0; c0 < kp; c0 += cw) {
+        const int w = std::min(cw, kp - c0);
+        if (w < cw && c0 > 0) HIPC(hipMemsetAsync(xc.p, 0, cbytes, ctx->stream));
+        copy_cols(ctx->nloc, w, ctx->d_rv, kp, c0, xc.d(), cw, 0, ctx->stream);
+        const int st = apply_A(ctx, xc.d(), 0, cw, yc.d(), nullptr, nullptr, nullptr);
+        if (st < 0) return st;
+        copy_cols(ctx->nloc, w, yc.d(), cw, 0, ctx->d_rw, kp, c0, ctx->stream);
+      }
+      HIPC(hipGetLastError());
+      HIPC(hipStreamSynchronize(ctx->stream));  // the chunk blocks leave scope
+    }
+    HIPC(hipGetLastError());
+  }
+  // H = V^T W
+  std::vector<double> h((size_t)kp * kp, 0.0);
+  if (ctx->nloc > 0) {
+    StageScope t(ctx, RBL_STAGE_RITZ);
+    const int splits = gram_splits(ctx->nloc, 1, kp, kp);
+    DevBuf slab, dH;
+    HIPC(hipMalloc(&slab.p, (size_t)splits * kp * kp * sizeof(double)));
+    HIPC(hipMalloc(&dH.p, (size_t)kp * kp * sizeof(double)));
+    gram_partial(ctx->nloc, run1(ctx->d_rv, kp), pan1(ctx->d_rw, kp), slab.d(), splits, nullptr, ctx->stream);
+    reduce_slab(slab.d(), splits, (int64_t)kp * kp, dH.d(), nullptr, ctx->stream);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(h.data(), dH.p, (size_t)kp * kp * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+  }
+  HIPC(hipStreamSynchronize(ctx->stream));
+  harvest_timers(ctx);
+  for (int r = 0; r < k; ++r)
+    for (int c = 0; c < k; ++c) H_out[(size_t)c * k + r] = h[(size_t)r * kp + c];
+  ctx->ritz_k = k;
+  return RBL_OK;
+}
+
+int rbl_ritz_finish(rbl_ctx* ctx, int k, const double* Y, const double* theta, double* V_out,
+                    double* resid_out) {
+  if (!ctx || k < 1 || !Y || !theta) return fail(ctx, RBL_ERR_INVALID, "rbl_ritz_finish: bad arguments");
+  if (!ctx->d_rv || !ctx->d_rw || ctx->ritz_k != k)
+    return fail(ctx, RBL_ERR_STATE, "rbl_ritz_finish: no rbl_ritz_project of this k precedes it");
+  HIPC(hipSetDevice(ctx->device));
+  const int kp = (k + 1) & ~1;
+  const int64_t nl = std::max<int64_t>(ctx->nloc, 1);
+  std::vector<double> yrm((size_t)kp * kp, 0.0), th(kp, 0.0), res(kp, 0.0);
+  for (int r = 0; r < k; ++r)
+    for (int c = 0; c < k; ++c) yrm[(size_t)r * kp + c] = Y[(size_t)c * k + r];
+  for (int c = 0; c < k; ++c) th[c] = theta[c];
+  const int grid = resid_grid(ctx->nloc);
+  DevBuf dY, dTh, X, Z, part, dres;
+  HIPC(hipMalloc(&dY.p, (size_t)kp * kp * sizeof(double)));
+  HIPC(hipMalloc(&dTh.p, kp * sizeof(double)));
+  HIPC(hipMalloc(&X.p, (size_t)nl * kp * sizeof(double)));
+  HIPC(hipMalloc(&Z.p, (size_t)nl * kp * sizeof(double)));
+  HIPC(hipMalloc(&part.p, (size_t)grid * kp * sizeof(double)));
+  HIPC(hipMalloc(&dres.p, kp * sizeof(double)));
+  HIPC(hipMemcpyAsync(dY.p, yrm.data(), (size_t)kp * kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dTh.p, th.data(), kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (ctx->nloc > 0) {
+    StageScope t(ctx, RBL_STAGE_RITZ);
+    // X = V Y, Z = W Y; resid_j^2 = sum_r (Z - X diag(theta))^2[r, j]
+    CHK(tsmm_checked(ctx, run1(ctx->d_rv, kp), dY.d(), kp, pan1(X.d(), kp), 1.0, 0.0, nullptr));
+    CHK(tsmm_checked(ctx, run1(ctx->d_rw, kp), dY.d(), kp, pan1(Z.d(), kp), 1.0, 0.0, nullptr));
+    resid_partial(ctx->nloc, kp, Z.d(), X.d(), dTh.d(), part.d(), grid, ctx->stream);
+    reduce_slab(part.d(), grid, kp, dres.d(), nullptr, ctx->stream);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(res.data(), dres.p, kp * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (V_out) {  // W is spent: its block takes the column-major copy of X
+      rowmajor_to_colmajor(X.d(), ctx->nloc, kp, ctx->d_rw, ctx->stream);
+      HIPC(hipGetLastError());
+      CHK(d2h_staged(ctx, V_out, ctx->d_rw, (size_t)ctx->nloc * k * sizeof(double)));
+    }
+  }
+  HIPC(hipStreamSynchronize(ctx->stream));
+  harvest_timers(ctx);
+  if (resid_out)
+    for (int c = 0; c < k; ++c) resid_out[c] = std::sqrt(res[c]);
+  hipFree(ctx->d_rv);
+  hipFree(ctx->d_rw);
+  ctx->d_rv = ctx->d_rw = nullptr;
+  ctx->ritz_k = 0;
   return RBL_OK;
 }
 

@@ -1,0 +1,177 @@
+// spmm_cheb.hip — the row passes of the Chebyshev-filtered operator and of Rayleigh-Ritz on A
+// (gfx950).
+//
+// The filter p(A) = T_d((A - cI)/e) / T_d((ref - c)/e) is applied by the scaled three-term
+// recurrence of Zhou and Saad (rbl_api.cpp cheb_apply): every term is one SpMM W = A Y_{j-1}
+// through whichever SpMM kernel the matrix runs, followed by ONE pass of cheb_axpby
+//
+//     Y_j = alpha W + beta Y_{j-1} (+ gamma Y_{j-2})
+//
+// over the n x b row-major blocks.  The blocks are contiguous (leading dimension b), so the
+// pass is a flat stream: 16-byte loads and stores when every block starts on a 16-byte boundary
+// (a basis slot starts at a multiple of n_local * b doubles, so an odd n_local * b leaves slots
+// 8-byte aligned: then the 8-byte form runs), a guarded last element when n * b is odd, and a
+// grid sized from the CU count, each thread walking the stream grid-stride.  Y_j may be written
+// over W (each thread reads an element of W before it writes it).
+//
+// resid_partial forms the per-workgroup partials of the column sums of (Z - X diag(theta))^2 —
+// the true residuals ||A v - theta v||^2 of rbl_ritz_finish — summed in a fixed order (each
+// thread over its rows ascending, then the workgroup's row groups ascending in LDS; reduce_slab
+// adds the workgroups in order): no float atomics, the same bits on every run.
+//
+// copy_cols moves a column range between row-major blocks of different widths (the column
+// chunks rbl_ritz_project multiplies by A).
+#include <algorithm>
+#include <mutex>
+
+#include "kernels.hpp"
+
+namespace rbl {
+
+namespace {
+
+constexpr int kChebThreads = 256;
+constexpr int kChebPerCu = 8;    // workgroups per CU of the stream pass (2 waves per SIMD x 4)
+constexpr int kResidPerCu = 4;
+constexpr int kResidMinRows = 64;  // rows per workgroup below which a smaller grid runs
+
+int cu_count() {
+  static std::mutex mu;
+  static int cus[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  std::lock_guard<std::mutex> g(mu);
+  if (cus[dev] == 0) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
+      v = 256;
+    cus[dev] = v;
+  }
+  return cus[dev];
+}
+
+// T = d2v: pairs (16 B), T = double: single elements.  npk: elements of type T; tail: one last
+// double past the pairs (or -1).
+template <typename T, bool HAS_Z>
+__global__ __launch_bounds__(kChebThreads) void k_cheb_axpby(int64_t npk, int64_t tail, const T* W,
+                                                             const T* __restrict__ Y,
+                                                             const T* __restrict__ Z, double alpha,
+                                                             double beta, double gamma, T* out) {
+  const int64_t stride = (int64_t)gridDim.x * kChebThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kChebThreads + threadIdx.x; i < npk; i += stride) {
+    T r = alpha * W[i] + beta * Y[i];
+    if constexpr (HAS_Z) r += gamma * Z[i];
+    out[i] = r;
+  }
+  if (tail >= 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+    const double* w = reinterpret_cast<const double*>(W);
+    const double* y = reinterpret_cast<const double*>(Y);
+    double r = alpha * w[tail] + beta * y[tail];
+    if constexpr (HAS_Z) r += gamma * reinterpret_cast<const double*>(Z)[tail];
+    reinterpret_cast<double*>(out)[tail] = r;
+  }
+}
+
+// CW columns x RG row groups per workgroup (CW * RG = 256, CW a power of two >= min(kp, 256))
+__global__ __launch_bounds__(kChebThreads) void k_resid_partial(int64_t nrows, int kp, int cw,
+                                                                const double* __restrict__ Z,
+                                                                const double* __restrict__ X,
+                                                                const double* __restrict__ theta,
+                                                                double* __restrict__ part) {
+  __shared__ double sm[kChebThreads];
+  const int rg = threadIdx.x / cw, c0 = threadIdx.x % cw, nrg = kChebThreads / cw;
+  const int64_t per = (nrows + gridDim.x - 1) / gridDim.x;
+  const int64_t r0 = (int64_t)blockIdx.x * per;
+  const int64_t r1 = r0 + per < nrows ? r0 + per : nrows;
+  auto colsum = [&](int c) {
+    const double th = theta[c];
+    double acc = 0.0;
+    for (int64_t r = r0 + rg; r < r1; r += nrg) {
+      const double d = Z[r * kp + c] - X[r * kp + c] * th;
+      acc += d * d;
+    }
+    return acc;
+  };
+  if (nrg == 1) {  // kp > 128: one thread per column (and per 256 columns), no LDS stage
+    for (int c = c0; c < kp; c += cw) part[(int64_t)blockIdx.x * kp + c] = colsum(c);
+    return;
+  }
+  // kp <= cw: one column per thread; every thread reaches the barrier
+  sm[threadIdx.x] = c0 < kp ? colsum(c0) : 0.0;
+  __syncthreads();
+  if (rg == 0 && c0 < kp) {
+    double s = 0.0;
+    for (int g = 0; g < nrg; ++g) s += sm[g * cw + c0];
+    part[(int64_t)blockIdx.x * kp + c0] = s;
+  }
+}
+
+__global__ __launch_bounds__(kChebThreads) void k_copy_cols(int64_t nrows, int w, const double* __restrict__ src,
+                                                            int lds, int s0, double* __restrict__ dst,
+                                                            int ldd, int d0) {
+  const int64_t total = nrows * w, stride = (int64_t)gridDim.x * kChebThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kChebThreads + threadIdx.x; i < total; i += stride) {
+    const int64_t r = i / w;
+    const int c = (int)(i - r * w);
+    dst[r * ldd + d0 + c] = src[r * lds + s0 + c];
+  }
+}
+
+int stream_grid(int64_t work_items, int per_cu) {
+  const int64_t want = (work_items + kChebThreads - 1) / kChebThreads;
+  const int64_t cap = (int64_t)cu_count() * per_cu;
+  return (int)std::max<int64_t>(1, std::min(want, cap));
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+void cheb_axpby(int64_t len, const double* W, const double* Y, const double* Z, double alpha,
+                double beta, double gamma, double* out, hipStream_t s) {
+  if (len <= 0) return;
+  const bool vec = aligned16(W) && aligned16(Y) && aligned16(out) && (!Z || aligned16(Z));
+  if (vec) {
+    const int64_t np = len / 2, tail = (len & 1) ? len - 1 : -1;
+    const int grid = stream_grid(np, kChebPerCu);
+    const d2v *w = reinterpret_cast<const d2v*>(W), *y = reinterpret_cast<const d2v*>(Y);
+    d2v* o = reinterpret_cast<d2v*>(out);
+    if (Z)
+      hipLaunchKernelGGL((k_cheb_axpby<d2v, true>), dim3(grid), dim3(kChebThreads), 0, s, np, tail, w, y,
+                         reinterpret_cast<const d2v*>(Z), alpha, beta, gamma, o);
+    else
+      hipLaunchKernelGGL((k_cheb_axpby<d2v, false>), dim3(grid), dim3(kChebThreads), 0, s, np, tail, w, y,
+                         static_cast<const d2v*>(nullptr), alpha, beta, gamma, o);
+    return;
+  }
+  const int grid = stream_grid(len, kChebPerCu);
+  if (Z)
+    hipLaunchKernelGGL((k_cheb_axpby<double, true>), dim3(grid), dim3(kChebThreads), 0, s, len,
+                       (int64_t)-1, W, Y, Z, alpha, beta, gamma, out);
+  else
+    hipLaunchKernelGGL((k_cheb_axpby<double, false>), dim3(grid), dim3(kChebThreads), 0, s, len,
+                       (int64_t)-1, W, Y, static_cast<const double*>(nullptr), alpha, beta, gamma, out);
+}
+
+int resid_grid(int64_t nrows) {
+  const int64_t by_rows = (nrows + kResidMinRows - 1) / kResidMinRows;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(by_rows, (int64_t)cu_count() * kResidPerCu));
+}
+
+void resid_partial(int64_t nrows, int kp, const double* Z, const double* X, const double* theta,
+                   double* part, int grid, hipStream_t s) {
+  int cw = 1;
+  while (cw < kp && cw < kChebThreads) cw *= 2;
+  hipLaunchKernelGGL(k_resid_partial, dim3(grid), dim3(kChebThreads), 0, s, nrows, kp, cw, Z, X, theta,
+                     part);
+}
+
+void copy_cols(int64_t nrows, int w, const double* src, int lds, int s0, double* dst, int ldd, int d0,
+               hipStream_t s) {
+  if (nrows <= 0 || w <= 0) return;
+  const int grid = stream_grid(nrows * w, kChebPerCu);
+  hipLaunchKernelGGL(k_copy_cols, dim3(grid), dim3(kChebThreads), 0, s, nrows, w, src, lds, s0, dst, ldd,
+                     d0);
+}
+
+}  // namespace rbl

@@ -1,7 +1,8 @@
 """rbl — MI355X-native Randomized Block Lanczos inner loop (host side).
 
 ``RBL_gpu(A, k, b)`` mirrors Julia/RBL_gpu.jl:205, ``RBL_svd(B, k, b)`` the truncated SVD of
-images.jl:20-33 on the implicit B^T B; ``Context`` wraps the C-ABI of
+images.jl:20-33 on the implicit B^T B, ``RBL_filtered(A, k, b, which="SA"|"LA")`` the smallest or
+largest eigenpairs through a Chebyshev filter; ``Context`` wraps the C-ABI of
 librbl_hip.so (include/rbl_hip.h).  Importing this package loads the HIP library and fails
 loudly if it has not been built: there is no CPU fallback.
 """
@@ -12,3 +13,4 @@ from .restarted import RBL_gpu_restarted, RBL_restarted  # noqa: F401
 from .rbl_gpu import (KRYL_SZ_GPU, RESIDUAL_TOL, Context, RBL_gpu, RBLInfo, LocalGroup,  # noqa: F401
                       lanczos, rccl_version)
 from .svd import RBL_svd  # noqa: F401
+from .filtered import RBL_filtered, cheb_scalars, filter_bounds, lanczos_filtered  # noqa: F401

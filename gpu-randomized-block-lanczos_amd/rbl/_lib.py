@@ -100,6 +100,10 @@ SIGNATURES = {
     "rbl_ritz": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd]),
     "rbl_get_block": (C.c_int, [_p, C.c_int, _pd]),
     "rbl_num_blocks": (C.c_int, [_p]),
+    "rbl_set_filter": (C.c_int, [_p, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "rbl_apply_filter": (C.c_int, [_p, C.c_int, _pd, _pd]),
+    "rbl_ritz_project": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd]),
+    "rbl_ritz_finish": (C.c_int, [_p, C.c_int, _pd, _pd, _pd, _pd]),
     "rbl_restart": (C.c_int, [_p, C.c_int, _pd]),
     "rbl_lock": (C.c_int, [_p, C.c_int, C.c_int, _pd]),
     "rbl_num_locked": (C.c_int, [_p]),

@@ -352,6 +352,44 @@ class Context:
     def num_blocks(self) -> int:
         return lib.rbl_num_blocks(self._h)
 
+    # ---- Chebyshev filter and Rayleigh-Ritz on A (rbl.filtered) ----
+    def set_filter(self, degree: int, lo: float = 0.0, hi: float = 0.0, ref: float = 0.0) -> None:
+        """rbl_set_filter: later start / step calls run on p(A) = T_d((A - c)/e) / T_d((ref - c)/e)
+        with [lo, hi] the damped interval; degree 0 clears the filter."""
+        self._check(lib.rbl_set_filter(self._h, int(degree), float(lo), float(hi), float(ref)),
+                    "rbl_set_filter")
+
+    def apply_filter(self, X: np.ndarray) -> np.ndarray:
+        """Y = p(A) X on the device (rbl_apply_filter); apply() stays the plain A X."""
+        n, r0, r1, _ = self.matrix_info()
+        X = np.asfortranarray(X, dtype=np.float64)
+        Y = np.zeros((r1 - r0, X.shape[1]), order="F")
+        self._check(lib.rbl_apply_filter(self._h, X.shape[1], dptr(X), dptr(Y)), "rbl_apply_filter")
+        return Y
+
+    def ritz_project(self, nblocks: int, k: int, S: np.ndarray) -> np.ndarray:
+        """rbl_ritz_project: V = [Q_1..Q_nblocks] S and W = A V stay on the device; returns
+        H = V^T W (k x k)."""
+        S = np.asfortranarray(S[: nblocks * self.b, :k], dtype=np.float64)
+        H = np.zeros((k, k), order="F")
+        self._check(lib.rbl_ritz_project(self._h, nblocks, k, dptr(S), dptr(H)), "rbl_ritz_project")
+        return H
+
+    def ritz_finish(self, Y: np.ndarray, theta: np.ndarray):
+        """rbl_ritz_finish with H = Y diag(theta) Y^T: returns (V Y, the true residual norms
+        ||A v_j - theta_j v_j||_2)."""
+        n, r0, r1, _ = self.matrix_info()
+        Y = np.asfortranarray(Y, dtype=np.float64)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        k = theta.size
+        if Y.shape != (k, k):
+            raise ValueError("ritz_finish: Y must be k x k and theta of length k")
+        V = np.zeros((r1 - r0, k), order="F")
+        res = np.zeros(k)
+        self._check(lib.rbl_ritz_finish(self._h, k, dptr(Y), dptr(theta), dptr(V), dptr(res)),
+                    "rbl_ritz_finish")
+        return V, res
+
     def timers(self) -> dict:
         names = _lib.stage_names()
         ms = np.zeros(len(names))

@@ -336,6 +336,40 @@ int rbl_ritz(rbl_ctx* ctx, int nblocks, int k, const double* S, double* V_out);
 int rbl_get_block(rbl_ctx* ctx, int j, double* Q_out);
 int rbl_num_blocks(rbl_ctx* ctx);
 
+/* ---- Chebyshev-filtered runs: the smallest or largest eigenpairs ---------------------------
+ * (No reference equivalent: the reference returns the largest-magnitude pairs only.)
+ * rbl_set_filter: with degree >= 1 every later rbl_start, rbl_step, rbl_step_async and restart
+ * cycle runs block Lanczos on
+ *     p(A) = T_d((A - c I) / e) / T_d((ref - c) / e),   c = (lo + hi) / 2,  e = (hi - lo) / 2,
+ * |p| <= 1 / |T_d((ref - c)/e)| on the damped interval [lo, hi], p(ref) = 1 and growing outside:
+ * the eigenvalues of A beyond `ref`'s end of the spectrum become the largest-magnitude ones of
+ * p(A).  Applied by the scaled three-term recurrence of Zhou and Saad (nothing overflows):
+ *     s_1 = e / (ref - c),  Y_1 = (s_1 / e) (A X - c X),
+ *     s' = 1 / (2 / s_1 - s),  Y_j = (2 s' / e) (A Y_{j-1} - c Y_{j-1}) - s s' Y_{j-2},  s = s',
+ * each term one SpMM (whichever kernel the matrix runs) and one row pass.  The step then forms
+ * U = p(A) Q_i - Q_{i-1} B_i^T; T holds p's eigenvalues, the Ritz vectors are A's eigenvectors
+ * (rbl_ritz_project / rbl_ritz_finish recover A's eigenvalues).  degree 0 clears the filter:
+ * every path is then the unfiltered one, bit for bit.  rbl_apply stays the plain A X.
+ * Limits (RBL_ERR_INVALID, before any collective or allocation): one rank only; the fp64 basis
+ * only (rbl_start with basis_bits = 32 while a filter is set); no rectangular B; degree >= 0;
+ * lo < hi; ref outside [lo, hi]; finite arguments. */
+int rbl_set_filter(rbl_ctx* ctx, int degree, double lo, double hi, double ref);
+/* Y = p(A) X for a host n_local x b column-major block (the convention of rbl_apply), with the
+ * filter set; RBL_ERR_STATE without one.  Timed under "AQ". */
+int rbl_apply_filter(rbl_ctx* ctx, int b, const double* X, double* Y);
+/* Rayleigh-Ritz on A with true residuals (also without a filter).
+ * rbl_ritz_project: V = [Q_1..Q_nblocks] S (S: (nblocks*b) x k column-major, host; orthonormal
+ *   columns) and W = A V (the plain operator) are formed and kept on the device; H_out (k x k
+ *   column-major, host) = V^T W.  k <= RBL_MAX_BLOCK; one rank; replaces an earlier projection.
+ * rbl_ritz_finish: with the host's eigendecomposition H = Y diag(theta) Y^T (Y: k x k
+ *   column-major), V_out (n_local x k column-major) = V Y and resid_out[j] =
+ *   || W y_j - theta_j V y_j ||_2, the true residual of the pair (theta_j, V y_j) — per-workgroup
+ *   partial sums added in a fixed order, no atomics.  Frees V and W.  RBL_ERR_STATE without a
+ *   preceding rbl_ritz_project (of the same k). */
+int rbl_ritz_project(rbl_ctx* ctx, int nblocks, int k, const double* S, double* H_out);
+int rbl_ritz_finish(rbl_ctx* ctx, int k, const double* Y, const double* theta, double* V_out,
+                    double* resid_out);
+
 /* ---- restarted variants (restarted.jl: RBL_gpu_restarted / RBL_restarted) ---------------
  * Locked Ritz vectors live on the device (Qlock_gpu); fp64 basis runs only.
  * rbl_restart: the next cycle starts from Q_1 = [Q_1..Q_nblocks] S (S: (nblocks*b) x b

@@ -15,6 +15,8 @@
 #   D, V = RBL_hip(A, k, b; device_blocks = -1)   # hybrid buffer: what fits in HBM, rest on host
 #   D, V = RBL_hip_restarted(A, k)       # restarted.jl:106 (RBL_gpu_restarted)
 #   U, D, V = RBL_gpu_svd(B, k, b)       # images.jl:29-33 on a sparse rectangular B, B^T B implicit
+#   D, V, r = RBL_gpu_filtered(A, k, b; which = :SA, degree = 8)   # the k smallest (or :LA largest)
+#                                        # pairs through a Chebyshev filter, r = ||A v - D v||
 #
 # Untested here: Julia is not installed in the build container (SURVEY §8(c)).  Every ccall
 # below is checked against include/rbl_hip.h by tests/test_julia_binding.py (argument count
@@ -324,6 +326,119 @@ function RBL_hip_restarted(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k
         L > 0 && rbl_check(ctx, ccall((:rbl_get_locked, librbl_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}),
                                       ctx, V), "rbl_get_locked")
         return D, V
+    finally
+        ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
+    end
+end
+
+# The k algebraically smallest (which = :SA) or largest (:LA) eigenpairs — eigsh's `which` —
+# through a Chebyshev filter (rbl_set_filter; no reference equivalent: RBL_gpu returns the
+# largest-magnitude pairs).  The same call sequence as rbl/filtered.py lanczos_filtered:
+#   1. s0 = max(8, cld(3k, b)) plain block steps; the Ritz values of T and their residual bounds
+#      give the damped interval [lo, hi] and the reference point ref (for :SA: hi = theta_max +
+#      its residual, lo = the (k+b)-th smallest Ritz value, ref = theta_min; :LA mirrored);
+#   2. rbl_set_filter, then the reference's loop and convergence test on the filtered T;
+#   3. Rayleigh-Ritz on A: rbl_ritz_project returns H = V^T A V for the k dominant Ritz vectors
+#      of p(A), the host solves H = Y Theta Y^T, rbl_ritz_finish returns V Y and the true
+#      residuals ||A v - theta v||.
+# Returns D (from the wanted end inward), V (n x k) and the residual norms.  One GPU, fp64 basis.
+function RBL_gpu_filtered(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k::Int64, b::Int64;
+                          which::Symbol = :SA, degree::Int = 8, device::Int = 0,
+                          seed::UInt64 = rand(UInt64), kryl_sz::Int64 = 1200)
+    which in (:SA, :LA) || throw(ArgumentError("which must be :SA or :LA"))
+    n = size(A, 2)
+    ctx = rbl_context(device)
+    set_filter!(d, lo, hi, ref) =
+        rbl_check(ctx, ccall((:rbl_set_filter, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble),
+                             ctx, Cint(d), lo, hi, ref), "rbl_set_filter")
+    # one run of the loop (RBL_gpu.jl:134-203) of at most m_cap steps: T, the last B, steps
+    function run(do_check::Bool, m_cap::Int64)
+        rbl_check(ctx, ccall((:rbl_start, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, UInt64),
+                             ctx, Cint(b), Cint(m_cap), Cint(64), C_NULL, seed), "rbl_start")
+        T = zeros(Float64, b + 1, 0)
+        Bl = zeros(Float64, b, b)
+        enqueued = 0
+        first = 1
+        i = 0
+        converged = false
+        while true
+            i += 1
+            is_check = do_check && i >= 2 && (i * b > k) && (mod(i, 4) == 0)
+            is_last = !(i * b < kryl_sz && i < m_cap)
+            (is_check || is_last) || continue
+            while enqueued < i
+                enqueued += 1
+                part = (enqueued >= 2 && mod(enqueued, 2) == 0) ? 1 : 0
+                rbl_check(ctx, ccall((:rbl_step_async, librbl_hip), Cint, (Ptr{Cvoid}, Cint, Cint),
+                                     ctx, Cint(enqueued), Cint(part)), "rbl_step_async")
+            end
+            m = i + 1 - first
+            Ah = zeros(Float64, b, b, m)
+            Bh = zeros(Float64, b, b, m)
+            sts = zeros(Cint, m)
+            rbl_check(ctx, ccall((:rbl_fetch, librbl_hip), Cint,
+                                 (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
+                                 ctx, Cint(first), Cint(i + 1), Ah, Bh, sts), "rbl_fetch")
+            for (jj, j) in enumerate(first:i)
+                Ai = Ah[:, :, jj]
+                Bl = Bh[:, :, jj]
+                T = j == 1 ? insertA!(Ai, b) : [T insertA!(Ai, b)]
+                if j == i && is_check
+                    D, V = dsbev('V', 'L', T)
+                    D, V = sort_eig_abs(D, V, k)
+                    if check_convergence(Bl, V, b, k, 1e-7)
+                        converged = true
+                        break
+                    end
+                end
+                (j < i || !is_last) && insertB!(Bl, T, b, j)
+            end
+            first = i + 1
+            (converged || is_last) && break
+        end
+        return T, Bl, i, converged
+    end
+    try
+        set_matrix!(ctx, A)
+        set_filter!(0, 0.0, 0.0, 0.0)
+        s0 = max(1, min(max(8, cld(3 * k, b)), n ÷ b))
+        T0, B0, _, _ = run(false, s0)
+        w, Z = dsbev('V', 'L', T0)                                 # ascending
+        res = [norm(B0 * Z[end-b+1:end, j]) for j in 1:length(w)]
+        length(w) >= k + b || throw(RblError(-1, "RBL_gpu_filtered: fewer than k + b Ritz values"))
+        lo, hi, ref = which == :SA ? (w[k+b], w[end] + res[end], w[1]) :
+                                     (w[1] - res[1], w[end-(k+b)+1], w[end])
+        set_filter!(degree, lo, hi, ref)
+        T, _, m, converged = run(true, cld(kryl_sz, b))
+        converged || @warn "RBL_gpu_filtered: not converged within kryl_sz=$kryl_sz (best effort)"
+        w, Z = dsbev('V', 'L', T)
+        w, Z = sort_eig_abs(w, Z, k)                               # the dominant pairs of p(A)
+        S = Matrix{Float64}(Z[:, end:-1:1])
+        for c in 1:size(S, 2)
+            p = argmax(abs.(S[:, c]))
+            S[p, c] < 0 && (S[:, c] .*= -1)
+        end
+        H = zeros(Float64, k, k)
+        rbl_check(ctx, ccall((:rbl_ritz_project, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}),
+                             ctx, Cint(m), Cint(k), S, H), "rbl_ritz_project")
+        F = eigen(Symmetric((H + H') / 2))                         # ascending
+        theta = Vector{Float64}(F.values)
+        Y = Matrix{Float64}(F.vectors)
+        if which == :LA
+            theta = theta[end:-1:1]
+            Y = Y[:, end:-1:1]
+        end
+        Vout = zeros(Float64, n, k)
+        resid = zeros(Float64, k)
+        rbl_check(ctx, ccall((:rbl_ritz_finish, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                             ctx, Cint(k), Y, theta, Vout, resid), "rbl_ritz_finish")
+        set_filter!(0, 0.0, 0.0, 0.0)
+        any(lo .<= theta .<= hi) && @warn "RBL_gpu_filtered: an eigenvalue returned lies in the damped interval"
+        return theta, Vout, resid
     finally
         ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
     end

@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""Time-to-k of the Chebyshev-filtered route (rbl.lanczos_filtered, which="SA") against the route
+available without it: RBL_gpu on the host-built  hi*I - A  (largest magnitude = smallest of A).
+
+Matrices (generated on the device): the circuit-like SPD matrix at its default size
+(n = 1,585,478, G3_circuit's shape; segmented gather) and a hash-window band matrix
+(n = 1e6, half-width 64; band tiles).  k = 20, b = 32, degrees 4 / 8 / 16, `--repeats` timed
+repeats after one warm-up of every route, the routes alternated within each repeat in one
+process; median and spread (min .. max) of the host wall time of the whole route — for the
+filtered route the estimation run, the filtered loop, its host eigensolves and the Rayleigh-Ritz
+step; for the shifted route the loop and rbl_ritz (its host-side build of hi*I - A and the second
+upload are NOT charged to it).  Both routes stop at the library's Krylov limit (--kryl, default
+1200 columns) when they have not converged; `converged`, the block steps and the largest true
+residual ||A v - theta v|| reached are recorded, so a capped run is visible as such.
+
+Per-term cost (hipEvents, the library's "AQ" stage timer): rbl_apply_filter at degrees 4 and 16 —
+(t16 - t4) / 12 is one recurrence term (SpMM + one row pass); the bare SpMM is the "AQ" stage of
+rbl_start plus step 1 (A * Omega and A * Q_1: no 3-term epilogue), halved.  The row pass of a term j >= 2
+reads three n x b blocks and writes one: 4 n b 8 bytes (term 1: 3 n b 8).
+
+Writes one JSON document (default profiles/filter_bench.json)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import scipy.sparse as sp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "gpu-randomized-block-lanczos_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def _stats(xs):
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "n": len(xs)}
+
+
+def _host_matrix(ctx):
+    n, r0, r1, nnz = ctx.matrix_info()
+    rowptr, col, val = ctx.get_matrix_csr()
+    return sp.csr_matrix((val, col, rowptr), shape=(n, n))
+
+
+def bench_matrix(rbl, name, gen, args):
+    from rbl import _lib
+    k, b = args.k, args.b
+    out = {"matrix": name, "k": k, "b": b, "kryl_sz": args.kryl, "repeats": args.repeats}
+    with rbl.Context(0) as ctx, rbl.Context(0) as sctx:
+        gen(ctx)
+        n, _, _, nnz = ctx.matrix_info()
+        out.update(n=n, nnz=nnz, spmm_kernel=ctx.spmm_kernel_for(b))
+        A = _host_matrix(ctx)
+        hi_g = float(abs(A).sum(axis=1).max())          # Gershgorin: lambda_max <= hi_g
+        sctx.set_matrix((sp.identity(n, format="csr") * hi_g - A).tocsr())
+        out["shift"] = hi_g
+
+        def shifted():
+            t0 = time.perf_counter()
+            D, V, info = rbl.lanczos(sctx, k, b, kryl_sz=args.kryl, seed=args.seed)
+            dt = time.perf_counter() - t0
+            theta = hi_g - D
+            res = np.linalg.norm(A @ V - V * theta, axis=0)
+            return dt, {"steps": info.iters, "est_steps": 0, "converged": bool(info.converged),
+                        "resid_true_max": float(res.max()), "theta_min": float(theta.min())}
+
+        def filtered(degree):
+            def run():
+                t0 = time.perf_counter()
+                D, V, info = rbl.lanczos_filtered(ctx, k, b, which="SA", degree=degree,
+                                                  kryl_sz=args.kryl, seed=args.seed)
+                dt = time.perf_counter() - t0
+                return dt, {"steps": info.iters, "est_steps": info.est_steps,
+                            "converged": bool(info.converged),
+                            "resid_true_max": float(np.max(info.resid_true)),
+                            "theta_min": float(D.min()), "filter": info.filter}
+            return run
+
+        routes = [("shifted", shifted)] + [(f"degree{d}", filtered(d)) for d in args.degrees]
+        times = {r: [] for r, _ in routes}
+        last = {}
+        for rep in range(-1, args.repeats):             # rep -1: warm-up, not recorded
+            for rname, fn in routes:
+                dt, rec = fn()
+                last[rname] = rec
+                if rep >= 0:
+                    times[rname].append(dt * 1e3)
+                print(f"{name} rep {rep} {rname}: {dt * 1e3:.1f} ms {rec}", flush=True)
+        out["routes"] = {r: {"time_ms": _stats(times[r]), **last[r]} for r, _ in routes}
+
+        # per-term cost from the library's "AQ" stage events
+        X = np.random.default_rng(1).standard_normal((n, b))
+        flt = next(v["filter"] for r, v in out["routes"].items() if r.startswith("degree"))
+        ctx.set_option(_lib.RBL_OPT_TIMERS, 2)
+        aq = {}
+        for d in (4, 16):
+            ctx.set_filter(d, flt["lo"], flt["hi"], flt["ref"])
+            ctx.apply_filter(X)                         # warm-up
+            ts = []
+            for _ in range(args.repeats):
+                ctx.reset_timers()
+                ctx.apply_filter(X)
+                ts.append(ctx.timers()["AQ"])
+            aq[d] = statistics.median(ts)
+        ctx.set_filter(0)
+        # the bare SpMM: rbl_start's A * Omega and step 1's A * Q_1 carry no 3-term epilogue
+        ts = []
+        for rep in range(-1, args.repeats):
+            ctx.reset_timers()
+            rbl.lanczos(ctx, k, b, check=False, max_steps=1, ritz=False, seed=args.seed,
+                        speculate=False)
+            ctx.synchronize()
+            if rep >= 0:
+                ts.append(ctx.timers()["AQ"] / 2.0)
+        ctx.set_option(_lib.RBL_OPT_TIMERS, 0)
+        term = (aq[16] - aq[4]) / 12.0
+        spmm = statistics.median(ts)
+        bytes_pass = 4 * n * b * 8
+        out["per_term"] = {"apply_filter_aq_ms": {str(d): aq[d] for d in aq}, "term_ms": term,
+                           "bare_spmm_ms": spmm, "pass_ms": term - spmm, "pass_bytes": bytes_pass,
+                           "pass_GBps": bytes_pass / (term - spmm) / 1e6 if term > spmm else None}
+        print(f"{name} per term: {out['per_term']}", flush=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--k", type=int, default=20)
+    ap.add_argument("--b", type=int, default=32)
+    ap.add_argument("--degrees", type=int, nargs="+", default=[4, 8, 16])
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--kryl", type=int, default=1200)
+    ap.add_argument("--seed", type=int, default=20261019)
+    ap.add_argument("--n-circuit", type=int, default=1_585_478)
+    ap.add_argument("--n-band", type=int, default=1_000_000)
+    ap.add_argument("--matrices", nargs="+", default=["circuit", "band"], choices=["circuit", "band"])
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "filter_bench.json"))
+    args = ap.parse_args()
+    import rbl
+    gens = {"circuit": lambda c: c.gen_circuit(args.n_circuit),
+            "band": lambda c: c.gen_hashwindow(args.n_band, 64, 0.78, 20261015)}
+    doc = {"tool": "tools/bench_filter.py", "which": "SA", "results": []}
+    for m in args.matrices:
+        doc["results"].append(bench_matrix(rbl, m, gens[m], args))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({"wrote": args.out}))
+
+
+if __name__ == "__main__":
+    main()
