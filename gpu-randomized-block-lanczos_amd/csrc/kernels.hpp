@@ -298,6 +298,14 @@ void band_positions(const CsrDev& A, uint16_t* pos, hipStream_t s);
 // accesses when every pointer is 16-byte aligned; the grid follows the CU count.
 void cheb_axpby(int64_t len, const double* W, const double* Y, const double* Z, double alpha,
                 double beta, double gamma, double* out, hipStream_t s);
+// One term of a Chebyshev series after its SpMM W = A T_{j-1}, fused with the accumulation:
+//   T_j = alpha W + beta T1 (- T2 unless first);  ACC += mu T_j  (first: ACC = mu0 T1 + mu T_j,
+//   ACC not read);  T_j stored to Tout unless last (Tout may be W; ACC aliases nothing).
+// Same stream conventions as cheb_axpby (16-byte form when every pointer used is 16-byte
+// aligned, guarded odd tail, grid from the CU count, no atomics).
+void cheb_series_term(int64_t len, const double* W, const double* T1, const double* T2, double alpha,
+                      double beta, double mu, double mu0, double* Tout, double* ACC, bool first,
+                      bool last, hipStream_t s);
 // part[g][c] = sum over workgroup g's rows of (Z[r][c] - X[r][c] theta[c])^2, c < kp (Z, X: n x kp
 // row-major), g < grid = resid_grid(nrows): a fixed summation order, no atomics; reduce_slab
 // over the grid gives the squared column norms.

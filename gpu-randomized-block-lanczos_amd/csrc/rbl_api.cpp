@@ -213,8 +213,13 @@ struct rbl_ctx {
   // and zeroed like every block an SpMM writes; sized at rbl_start
   int filt_deg = 0;
   double filt_lo = 0.0, filt_hi = 0.0, filt_ref = 0.0;
-  double* d_filt[2] = {nullptr, nullptr};
+  double* d_filt[3] = {nullptr, nullptr, nullptr};
   int filt_cols = 0;
+  // Chebyshev series (rbl_set_filter_series; empty: none): p(A) = sum_j ser_mu[j] T_j((A - c)/e)
+  // over [ser_lo, ser_hi]; its recurrence rotates through three work blocks (d_filt[2] is
+  // allocated only while a series is set).  At most one of filt_deg > 0 and a series holds.
+  std::vector<double> ser_mu;
+  double ser_lo = 0.0, ser_hi = 0.0;
   // Rayleigh-Ritz on A between rbl_ritz_project and rbl_ritz_finish: V = [Q_1..Q_m] S and
   // W = A V, (n_local + kRowPad) x ritz_kp row-major (ritz_kp = ritz_k rounded up to even)
   double* d_rv = nullptr;
@@ -1631,8 +1636,21 @@ int apply_A(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* U, cons
 
 // The two work blocks of the filter recurrence for block size b (allocated and zeroed like d_U:
 // the band kernels store unguarded into the kRowPad spare rows).
+// A series (rbl_set_filter_series) rotates through a third block, allocated only while one is set.
+bool has_series(const rbl_ctx* ctx) { return !ctx->ser_mu.empty(); }
+bool has_filter(const rbl_ctx* ctx) { return ctx->filt_deg > 0 || has_series(ctx); }
+
 int ensure_filter_bufs(rbl_ctx* ctx, int b) {
-  if (ctx->d_filt[0] && ctx->d_filt[1] && ctx->filt_cols >= b) return RBL_OK;
+  const int want = has_series(ctx) ? 3 : 2;
+  if (ctx->d_filt[0] && ctx->d_filt[1] && ctx->filt_cols >= b) {
+    if (want == 2 || ctx->d_filt[2]) return RBL_OK;
+    // the two blocks of an earlier filter stay; the series' third joins them at their width
+    const size_t bytes =
+        (size_t)(std::max<int64_t>(ctx->nloc, 1) + kRowPad) * ctx->filt_cols * sizeof(double);
+    HIPC(hipMalloc(&ctx->d_filt[2], bytes));
+    HIPC(hipMemsetAsync(ctx->d_filt[2], 0, bytes, ctx->stream));
+    return RBL_OK;
+  }
   HIPC(hipStreamSynchronize(ctx->stream));
   const size_t bytes = (size_t)(std::max<int64_t>(ctx->nloc, 1) + kRowPad) * b * sizeof(double);
   for (double*& p : ctx->d_filt) {
@@ -1640,9 +1658,9 @@ int ensure_filter_bufs(rbl_ctx* ctx, int b) {
     p = nullptr;
   }
   ctx->filt_cols = 0;
-  for (double*& p : ctx->d_filt) {
-    HIPC(hipMalloc(&p, bytes));
-    HIPC(hipMemsetAsync(p, 0, bytes, ctx->stream));
+  for (int q = 0; q < want; ++q) {
+    HIPC(hipMalloc(&ctx->d_filt[q], bytes));
+    HIPC(hipMemsetAsync(ctx->d_filt[q], 0, bytes, ctx->stream));
   }
   ctx->filt_cols = b;
   return RBL_OK;
@@ -1689,6 +1707,39 @@ int cheb_apply(rbl_ctx* ctx, const double* X, int b, double* out, double* F0, do
     y1 = yj;
   }
   return RBL_OK;
+}
+
+// out = sum_{j=0..d} mu_j T_j((A - cI)/e) X (rbl_set_filter_series), one rank: X, out and the
+// work blocks F[0..2] are distinct n_local x b row-major blocks; F[] carry the kRowPad spare
+// rows (the SpMMs write them), out is only streamed.  X is only read: it is T_0, so T_{j-1} of
+// term 1 and T_{j-2} of term 2.  T_j lives in F[j % 3]: term j's SpMM writes W = A T_{j-1} into
+// the block that held T_{j-3} (dead by then) and the fused pass turns W into T_j in place while
+// it adds mu_j T_j to out; the first pass initialises out, the last stores no T_d.
+int series_apply(rbl_ctx* ctx, const double* X, int b, double* out, double* const F[3]) {
+  if (ctx->nloc <= 0) return RBL_OK;
+  const std::vector<double>& mu = ctx->ser_mu;
+  const int d = (int)mu.size() - 1;
+  const double c = 0.5 * (ctx->ser_lo + ctx->ser_hi), e = 0.5 * (ctx->ser_hi - ctx->ser_lo);
+  const double* t1 = X;        // T_{j-1}
+  const double* t2 = nullptr;  // T_{j-2}
+  const int64_t len = ctx->nloc * b;
+  for (int j = 1; j <= d; ++j) {
+    double* tj = F[j % 3];
+    const int st = apply_A(ctx, t1, 0, b, tj, nullptr, nullptr, nullptr);
+    if (st < 0) return st;
+    const double al = (j == 1 ? 1.0 : 2.0) / e;
+    cheb_series_term(len, tj, t1, t2, al, -al * c, mu[j], mu[0], tj, out, j == 1, j == d, ctx->stream);
+    HIPC(hipGetLastError());
+    t2 = t1;
+    t1 = tj;
+  }
+  return RBL_OK;
+}
+
+// out = p(A) X with whichever filter is set (has_filter; the work blocks from ensure_filter_bufs)
+int filter_apply(rbl_ctx* ctx, const double* X, int b, double* out, double* const F[3]) {
+  if (has_series(ctx)) return series_apply(ctx, X, b, out, F);
+  return cheb_apply(ctx, X, b, out, F[0], F[1]);
 }
 
 // X -= l (l^T X) for every locked vector l in lock order (restarted.jl:1-21,
@@ -2250,8 +2301,8 @@ void free_run(rbl_ctx* ctx) {
   hipFree(ctx->d_flags); ctx->d_flags = nullptr;
   hipFree(ctx->d_lock); ctx->d_lock = nullptr;
   ctx->nlock = ctx->lock_cap = 0;
-  hipFree(ctx->d_filt[0]); hipFree(ctx->d_filt[1]);
-  ctx->d_filt[0] = ctx->d_filt[1] = nullptr;
+  hipFree(ctx->d_filt[0]); hipFree(ctx->d_filt[1]); hipFree(ctx->d_filt[2]);
+  ctx->d_filt[0] = ctx->d_filt[1] = ctx->d_filt[2] = nullptr;
   ctx->filt_cols = 0;
   hipFree(ctx->d_rv); ctx->d_rv = nullptr;
   hipFree(ctx->d_rw); ctx->d_rw = nullptr;
@@ -3211,6 +3262,12 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   if (ctx->filt_deg > 0 && (ctx->rect || ctx->nranks > 1))
     return fail(ctx, RBL_ERR_INVALID, "rbl_start: a Chebyshev filter (rbl_set_filter) runs on one rank "
                                       "and a square A only");
+  if (has_series(ctx) && basis_bits != 64)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_start: a Chebyshev series (rbl_set_filter_series) needs the "
+                                      "fp64 basis (basis_bits = 64)");
+  if (has_series(ctx) && (ctx->rect || ctx->nranks > 1))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_start: a Chebyshev series (rbl_set_filter_series) runs on "
+                                      "one rank and a square A only");
   HIPC(hipSetDevice(ctx->device));
   HIPC(hipStreamSynchronize(ctx->stream));
   // a repeated run with the same shape reuses the HBM plan (allocating ~100 GB of basis
@@ -3354,7 +3411,7 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
       return fail(ctx, RBL_ERR_OOM, "rbl_start: push buffers (injected by RBL_FAULT_PUSH_ALLOC)");
     CHK(ensure_push(ctx, b));
   }
-  if (ctx->filt_deg > 0) CHK(ensure_filter_bufs(ctx, b));
+  if (has_filter(ctx)) CHK(ensure_filter_bufs(ctx, b));
   return RBL_OK;
   }();
   if (ctx->nranks > 1) {
@@ -3392,8 +3449,8 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   CHK(halo_exchange(ctx, ctx->d_T, &Qin, &off));
   {
     StageScope t(ctx, RBL_STAGE_AQ);
-    if (ctx->filt_deg > 0)  // Q_1 = qr(p(A) Omega).Q
-      CHK(cheb_apply(ctx, ctx->d_T, b, ctx->d_U, ctx->d_filt[0], ctx->d_filt[1]));
+    if (has_filter(ctx))  // Q_1 = qr(p(A) Omega).Q
+      CHK(filter_apply(ctx, ctx->d_T, b, ctx->d_U, ctx->d_filt));
     else
       CHK(apply_A(ctx, Qin, off, b, ctx->d_U, nullptr, nullptr, nullptr));
     HIPC(hipGetLastError());
@@ -3557,7 +3614,7 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
   // fuse bit 2: the update itself rides on the SpMM below, which stages Q_i's rows corrected
   // (fp64 basis, band tiles at b = 32; no collective depends on the choice)
   // (not with a Chebyshev filter: the staging fusion assumes U = A Q_i from one SpMM)
-  const bool filt = ctx->filt_deg > 0;
+  const bool filt = has_filter(ctx);
   const bool lfuse = !f32 && i >= 2 && (ctx->fuse & 4) && fused && !ctx->dense && ctx->nloc > 0 &&
                      !filt && rbl_spmm_kernel_for(ctx, b) == 5 && spmm_bt_locfix_ok(csr(ctx), b);
   const double* Cloc = nullptr;
@@ -3602,7 +3659,7 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
                                         "the fp64 basis");
     CHK(ensure_filter_bufs(ctx, b));
     StageScope t(ctx, RBL_STAGE_AQ);
-    CHK(cheb_apply(ctx, Qi, b, ctx->d_U, ctx->d_filt[0], ctx->d_filt[1]));
+    CHK(filter_apply(ctx, Qi, b, ctx->d_U, ctx->d_filt));
     if (i >= 2) {
       transpose_small(smallp(ctx, S_BPREV), smallp(ctx, S_BT), b, ctx->stream);
       CHK(tsmm_checked(ctx, run1(Qm, b), smallp(ctx, S_BT), b, pan1(ctx->d_U, b), -1.0, 1.0, nullptr));
@@ -4010,8 +4067,9 @@ int rbl_ritz(rbl_ctx* ctx, int nblocks, int k, const double* S, double* V_out) {
 int rbl_set_filter(rbl_ctx* ctx, int degree, double lo, double hi, double ref) {
   if (!ctx) return RBL_ERR_INVALID;
   if (degree < 0) return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter: degree must be >= 0");
-  if (degree == 0) {
+  if (degree == 0) {  // clears either kind of filter
     ctx->filt_deg = 0;
+    ctx->ser_mu.clear();
     return RBL_OK;
   }
   if (!std::isfinite(lo) || !std::isfinite(hi) || !std::isfinite(ref))
@@ -4029,6 +4087,32 @@ int rbl_set_filter(rbl_ctx* ctx, int degree, double lo, double hi, double ref) {
   ctx->filt_lo = lo;
   ctx->filt_hi = hi;
   ctx->filt_ref = ref;
+  ctx->ser_mu.clear();  // replaces a series
+  ctx->cloc_step = 0;  // the operator changes: no Gram of an earlier step carries over
+  return RBL_OK;
+}
+
+int rbl_set_filter_series(rbl_ctx* ctx, int degree, double lo, double hi, const double* mu) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (degree < 1 || degree > 65535)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter_series: degree must be in [1, 65535]");
+  if (!std::isfinite(lo) || !std::isfinite(hi))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter_series: lo and hi must be finite");
+  if (!(lo < hi)) return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter_series: needs lo < hi");
+  if (!mu) return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter_series: mu is NULL");
+  for (int j = 0; j <= degree; ++j)
+    if (!std::isfinite(mu[j]))
+      return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter_series: mu[" + std::to_string(j) + "] is not finite");
+  if (ctx->nranks > 1)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter_series: one rank only (nranks > 1 is not supported)");
+  if (ctx->rect)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter_series: not with a rectangular B (rbl_set_matrix_normal)");
+  if (ctx->d_basis32)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_filter_series: the fp64 basis only (the current run has basis_bits = 32)");
+  ctx->ser_mu.assign(mu, mu + degree + 1);
+  ctx->ser_lo = lo;
+  ctx->ser_hi = hi;
+  ctx->filt_deg = 0;  // replaces a single-polynomial filter
   ctx->cloc_step = 0;  // the operator changes: no Gram of an earlier step carries over
   return RBL_OK;
 }
@@ -4037,30 +4121,76 @@ int rbl_apply_filter(rbl_ctx* ctx, int b, const double* X, double* Y) {
   if (!ctx || b < 1 || b > RBL_MAX_BLOCK || !X || !Y)
     return fail(ctx, RBL_ERR_INVALID, "rbl_apply_filter: bad arguments");
   if (!has_matrix(ctx)) return fail(ctx, RBL_ERR_STATE, "rbl_apply_filter: no matrix");
-  if (ctx->filt_deg < 1) return fail(ctx, RBL_ERR_STATE, "rbl_apply_filter: no filter set (rbl_set_filter)");
+  if (!has_filter(ctx))
+    return fail(ctx, RBL_ERR_STATE, "rbl_apply_filter: no filter set (rbl_set_filter / rbl_set_filter_series)");
   if (ctx->nranks > 1 || ctx->rect)
     return fail(ctx, RBL_ERR_INVALID, "rbl_apply_filter: one rank and a square A only");
   HIPC(hipSetDevice(ctx->device));
   const int64_t nl = std::max<int64_t>(ctx->nloc, 1);
   const size_t padded = (size_t)(nl + kRowPad) * b * sizeof(double);
-  DevBuf x, xr, y, f0, f1;
+  DevBuf x, xr, y, f0, f1, f2;
   HIPC(hipMalloc(&x.p, nl * b * sizeof(double)));
   HIPC(hipMalloc(&xr.p, nl * b * sizeof(double)));
-  for (DevBuf* p : {&y, &f0, &f1}) {
+  for (DevBuf* p : {&y, &f0, &f1, &f2}) {
+    if (p == &f2 && !has_series(ctx)) continue;  // the series' third block
     HIPC(hipMalloc(&p->p, padded));
     HIPC(hipMemsetAsync(p->p, 0, padded, ctx->stream));
   }
+  double* const F[3] = {f0.d(), f1.d(), f2.d()};
   HIPC(hipMemcpyAsync(x.p, X, ctx->nloc * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   colmajor_to_rowmajor(x.d(), ctx->nloc, b, xr.d(), ctx->stream);
   {
     StageScope t(ctx, RBL_STAGE_AQ);
-    CHK(cheb_apply(ctx, xr.d(), b, y.d(), f0.d(), f1.d()));
+    CHK(filter_apply(ctx, xr.d(), b, y.d(), F));
   }
   HIPC(hipGetLastError());
   rowmajor_to_colmajor(y.d(), ctx->nloc, b, x.d(), ctx->stream);
   HIPC(hipMemcpyAsync(Y, x.p, ctx->nloc * b * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   harvest_timers(ctx);
+  return RBL_OK;
+}
+
+// Diagnostics (tools/bench_filter.py --series): hipEvent time per pass of the fused series pass
+// (a middle term: reads W, T_{j-1}, T_{j-2}, ACC; writes T_j over W, ACC) and of the pair of
+// cheb_axpby launches it replaces (the term, then ACC = ACC + mu T_j), on blocks of `len`
+// doubles.  The coefficients keep the values bounded over any number of repeats.
+int rbl_bench_series_pass(rbl_ctx* ctx, int64_t len, int reps, double* fused_ms, double* pair_ms) {
+  if (!ctx || len < 1 || reps < 1 || !fused_ms || !pair_ms)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_series_pass: bad arguments");
+  HIPC(hipSetDevice(ctx->device));
+  DevBuf w, t1, t2, acc;
+  const size_t bytes = (size_t)len * sizeof(double);
+  for (DevBuf* p : {&w, &t1, &t2, &acc}) {
+    HIPC(hipMalloc(&p->p, bytes));
+    HIPC(hipMemsetAsync(p->p, 0, bytes, ctx->stream));
+  }
+  const double al = 0.5, be = 0.25, mu = 1e-3;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  auto fused = [&] {
+    cheb_series_term(len, w.d(), t1.d(), t2.d(), al, be, mu, 0.0, w.d(), acc.d(), false, false, ctx->stream);
+  };
+  auto pair = [&] {
+    cheb_axpby(len, w.d(), t1.d(), t2.d(), al, be, -1.0, w.d(), ctx->stream);
+    cheb_axpby(len, acc.d(), w.d(), nullptr, 1.0, mu, 0.0, acc.d(), ctx->stream);  // out may be W
+  };
+  int st = RBL_OK;
+  auto timed = [&](auto&& fn, double* out) {
+    fn();  // warm-up
+    if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+    for (int r = 0; r < reps; ++r) fn();
+    if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+    *out = (double)ms / reps;
+  };
+  timed(fused, fused_ms);
+  timed(pair, pair_ms);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_series_pass: a HIP call failed");
   return RBL_OK;
 }
 
@@ -4157,28 +4287,40 @@ int rbl_ritz_finish(rbl_ctx* ctx, int k, const double* Y, const double* theta, d
   if (!ctx || k < 1 || !Y || !theta) return fail(ctx, RBL_ERR_INVALID, "rbl_ritz_finish: bad arguments");
   if (!ctx->d_rv || !ctx->d_rw || ctx->ritz_k != k)
     return fail(ctx, RBL_ERR_STATE, "rbl_ritz_finish: no rbl_ritz_project of this k precedes it");
+  return rbl_ritz_finish_cols(ctx, k, k, Y, theta, V_out, resid_out);
+}
+
+// The projected width kproj (rows of Y, padded to kpr) and the kept pairs k (columns of Y, padded
+// to kp): with kproj == k every buffer and launch is rbl_ritz_finish's of before.
+int rbl_ritz_finish_cols(rbl_ctx* ctx, int kproj, int k, const double* Y, const double* theta,
+                         double* V_out, double* resid_out) {
+  if (!ctx || k < 1 || kproj < k || !Y || !theta)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_ritz_finish_cols: bad arguments (needs 1 <= k <= kproj)");
+  if (!ctx->d_rv || !ctx->d_rw || ctx->ritz_k != kproj)
+    return fail(ctx, RBL_ERR_STATE, "rbl_ritz_finish_cols: no rbl_ritz_project of this kproj precedes it");
   HIPC(hipSetDevice(ctx->device));
+  const int kpr = (kproj + 1) & ~1;
   const int kp = (k + 1) & ~1;
   const int64_t nl = std::max<int64_t>(ctx->nloc, 1);
-  std::vector<double> yrm((size_t)kp * kp, 0.0), th(kp, 0.0), res(kp, 0.0);
-  for (int r = 0; r < k; ++r)
-    for (int c = 0; c < k; ++c) yrm[(size_t)r * kp + c] = Y[(size_t)c * k + r];
+  std::vector<double> yrm((size_t)kpr * kp, 0.0), th(kp, 0.0), res(kp, 0.0);
+  for (int r = 0; r < kproj; ++r)
+    for (int c = 0; c < k; ++c) yrm[(size_t)r * kp + c] = Y[(size_t)c * kproj + r];
   for (int c = 0; c < k; ++c) th[c] = theta[c];
   const int grid = resid_grid(ctx->nloc);
   DevBuf dY, dTh, X, Z, part, dres;
-  HIPC(hipMalloc(&dY.p, (size_t)kp * kp * sizeof(double)));
+  HIPC(hipMalloc(&dY.p, (size_t)kpr * kp * sizeof(double)));
   HIPC(hipMalloc(&dTh.p, kp * sizeof(double)));
   HIPC(hipMalloc(&X.p, (size_t)nl * kp * sizeof(double)));
   HIPC(hipMalloc(&Z.p, (size_t)nl * kp * sizeof(double)));
   HIPC(hipMalloc(&part.p, (size_t)grid * kp * sizeof(double)));
   HIPC(hipMalloc(&dres.p, kp * sizeof(double)));
-  HIPC(hipMemcpyAsync(dY.p, yrm.data(), (size_t)kp * kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dY.p, yrm.data(), (size_t)kpr * kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipMemcpyAsync(dTh.p, th.data(), kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if (ctx->nloc > 0) {
     StageScope t(ctx, RBL_STAGE_RITZ);
     // X = V Y, Z = W Y; resid_j^2 = sum_r (Z - X diag(theta))^2[r, j]
-    CHK(tsmm_checked(ctx, run1(ctx->d_rv, kp), dY.d(), kp, pan1(X.d(), kp), 1.0, 0.0, nullptr));
-    CHK(tsmm_checked(ctx, run1(ctx->d_rw, kp), dY.d(), kp, pan1(Z.d(), kp), 1.0, 0.0, nullptr));
+    CHK(tsmm_checked(ctx, run1(ctx->d_rv, kpr), dY.d(), kp, pan1(X.d(), kp), 1.0, 0.0, nullptr));
+    CHK(tsmm_checked(ctx, run1(ctx->d_rw, kpr), dY.d(), kp, pan1(Z.d(), kp), 1.0, 0.0, nullptr));
     resid_partial(ctx->nloc, kp, Z.d(), X.d(), dTh.d(), part.d(), grid, ctx->stream);
     reduce_slab(part.d(), grid, kp, dres.d(), nullptr, ctx->stream);
     HIPC(hipGetLastError());

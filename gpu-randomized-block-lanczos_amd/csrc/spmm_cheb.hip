@@ -14,6 +14,12 @@
 // grid sized from the CU count, each thread walking the stream grid-stride.  Y_j may be written
 // over W (each thread reads an element of W before it writes it).
 //
+// cheb_series_term is the row pass of a general Chebyshev series sum_j mu_j T_j((A - cI)/e)
+// (rbl_set_filter_series; rbl_api.cpp series_apply): the unscaled recurrence term and the
+// accumulation into the result in one sweep — 4 reads + 2 writes per element (W, T_{j-1},
+// T_{j-2}, ACC; T_j, ACC) against the 5 + 2 of cheb_axpby followed by a second cheb_axpby as
+// the accumulate, and one launch instead of two.
+//
 // resid_partial forms the per-workgroup partials of the column sums of (Z - X diag(theta))^2 —
 // the true residuals ||A v - theta v||^2 of rbl_ritz_finish — summed in a fixed order (each
 // thread over its rows ascending, then the workgroup's row groups ascending in LDS; reduce_slab
@@ -70,6 +76,61 @@ __global__ __launch_bounds__(kChebThreads) void k_cheb_axpby(int64_t npk, int64_
     if constexpr (HAS_Z) r += gamma * reinterpret_cast<const double*>(Z)[tail];
     reinterpret_cast<double*>(out)[tail] = r;
   }
+}
+
+// One term of the Chebyshev series out = sum_j mu_j T_j (rbl_set_filter_series) after its SpMM
+// W = A T_{j-1}, the same stream conventions as k_cheb_axpby:
+//     T_j = alpha W + beta T_{j-1} (- T_{j-2}),   ACC (+)= mu_j T_j.
+// FIRST (j = 1): T_{j-1} = X, no T_{j-2}, and ACC = mu_0 X + mu_1 T_1 (ACC is not read).
+// LAST (j = d): T_d is not stored.  Tout may be W (each thread reads W[i] before it writes it);
+// ACC is distinct from every other block.
+template <typename T, bool FIRST, bool LAST>
+__global__ __launch_bounds__(kChebThreads) void k_cheb_series(int64_t npk, int64_t tail, const T* W,
+                                                              const T* __restrict__ T1,
+                                                              const T* __restrict__ T2, double alpha,
+                                                              double beta, double mu, double mu0,
+                                                              T* Tout, T* __restrict__ ACC) {
+  const int64_t stride = (int64_t)gridDim.x * kChebThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kChebThreads + threadIdx.x; i < npk; i += stride) {
+    const T t1 = T1[i];
+    T t = alpha * W[i] + beta * t1;
+    if constexpr (FIRST) {
+      ACC[i] = mu0 * t1 + mu * t;
+    } else {
+      t -= T2[i];
+      ACC[i] += mu * t;
+    }
+    if constexpr (!LAST) Tout[i] = t;
+  }
+  if (tail >= 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+    const double t1 = reinterpret_cast<const double*>(T1)[tail];
+    double t = alpha * reinterpret_cast<const double*>(W)[tail] + beta * t1;
+    double* acc = reinterpret_cast<double*>(ACC);
+    if constexpr (FIRST) {
+      acc[tail] = mu0 * t1 + mu * t;
+    } else {
+      t -= reinterpret_cast<const double*>(T2)[tail];
+      acc[tail] += mu * t;
+    }
+    if constexpr (!LAST) reinterpret_cast<double*>(Tout)[tail] = t;
+  }
+}
+
+template <typename T>
+void launch_cheb_series(int grid, int64_t npk, int64_t tail, const double* W, const double* T1,
+                        const double* T2, double alpha, double beta, double mu, double mu0,
+                        double* Tout, double* ACC, bool first, bool last, hipStream_t s) {
+  const T *w = reinterpret_cast<const T*>(W), *t1 = reinterpret_cast<const T*>(T1),
+          *t2 = reinterpret_cast<const T*>(T2);
+  T *to = reinterpret_cast<T*>(Tout), *acc = reinterpret_cast<T*>(ACC);
+#define RBL_SERIES_LAUNCH(F, L)                                                                    \
+  hipLaunchKernelGGL((k_cheb_series<T, F, L>), dim3(grid), dim3(kChebThreads), 0, s, npk, tail, w, \
+                     t1, t2, alpha, beta, mu, mu0, to, acc)
+  if (first && last) RBL_SERIES_LAUNCH(true, true);
+  else if (first) RBL_SERIES_LAUNCH(true, false);
+  else if (last) RBL_SERIES_LAUNCH(false, true);
+  else RBL_SERIES_LAUNCH(false, false);
+#undef RBL_SERIES_LAUNCH
 }
 
 // CW columns x RG row groups per workgroup (CW * RG = 256, CW a power of two >= min(kp, 256))
@@ -151,6 +212,22 @@ void cheb_axpby(int64_t len, const double* W, const double* Y, const double* Z, 
   else
     hipLaunchKernelGGL((k_cheb_axpby<double, false>), dim3(grid), dim3(kChebThreads), 0, s, len,
                        (int64_t)-1, W, Y, static_cast<const double*>(nullptr), alpha, beta, gamma, out);
+}
+
+void cheb_series_term(int64_t len, const double* W, const double* T1, const double* T2, double alpha,
+                      double beta, double mu, double mu0, double* Tout, double* ACC, bool first,
+                      bool last, hipStream_t s) {
+  if (len <= 0) return;
+  const bool vec = aligned16(W) && aligned16(T1) && aligned16(ACC) && (first || aligned16(T2)) &&
+                   (last || aligned16(Tout));
+  if (vec) {
+    const int64_t np = len / 2, tail = (len & 1) ? len - 1 : -1;
+    launch_cheb_series<d2v>(stream_grid(np, kChebPerCu), np, tail, W, T1, T2, alpha, beta, mu, mu0,
+                            Tout, ACC, first, last, s);
+    return;
+  }
+  launch_cheb_series<double>(stream_grid(len, kChebPerCu), len, (int64_t)-1, W, T1, T2, alpha, beta,
+                             mu, mu0, Tout, ACC, first, last, s);
 }
 
 int resid_grid(int64_t nrows) {

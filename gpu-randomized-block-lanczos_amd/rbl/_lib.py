@@ -101,9 +101,12 @@ SIGNATURES = {
     "rbl_get_block": (C.c_int, [_p, C.c_int, _pd]),
     "rbl_num_blocks": (C.c_int, [_p]),
     "rbl_set_filter": (C.c_int, [_p, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "rbl_set_filter_series": (C.c_int, [_p, C.c_int, C.c_double, C.c_double, _pd]),
     "rbl_apply_filter": (C.c_int, [_p, C.c_int, _pd, _pd]),
+    "rbl_bench_series_pass": (C.c_int, [_p, _i64, C.c_int, _pd, _pd]),
     "rbl_ritz_project": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd]),
     "rbl_ritz_finish": (C.c_int, [_p, C.c_int, _pd, _pd, _pd, _pd]),
+    "rbl_ritz_finish_cols": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd, _pd, _pd]),
     "rbl_restart": (C.c_int, [_p, C.c_int, _pd]),
     "rbl_lock": (C.c_int, [_p, C.c_int, C.c_int, _pd]),
     "rbl_num_locked": (C.c_int, [_p]),

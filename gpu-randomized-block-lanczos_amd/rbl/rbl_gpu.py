@@ -359,6 +359,14 @@ class Context:
         self._check(lib.rbl_set_filter(self._h, int(degree), float(lo), float(hi), float(ref)),
                     "rbl_set_filter")
 
+    def set_filter_series(self, lo: float, hi: float, mu) -> None:
+        """rbl_set_filter_series: later start / step calls run on the Chebyshev series p(A) =
+        sum_j mu[j] T_j((A - c)/e) with [lo, hi] enclosing the whole spectrum (degree =
+        len(mu) - 1 >= 1).  Replaces a set_filter; set_filter(0) clears it."""
+        mu = np.ascontiguousarray(mu, dtype=np.float64).ravel()
+        self._check(lib.rbl_set_filter_series(self._h, int(mu.size) - 1, float(lo), float(hi), dptr(mu)),
+                    "rbl_set_filter_series")
+
     def apply_filter(self, X: np.ndarray) -> np.ndarray:
         """Y = p(A) X on the device (rbl_apply_filter); apply() stays the plain A X."""
         n, r0, r1, _ = self.matrix_info()
@@ -377,17 +385,22 @@ class Context:
 
     def ritz_finish(self, Y: np.ndarray, theta: np.ndarray):
         """rbl_ritz_finish with H = Y diag(theta) Y^T: returns (V Y, the true residual norms
-        ||A v_j - theta_j v_j||_2)."""
+        ||A v_j - theta_j v_j||_2).  Y may hold only k chosen columns of the projected width kk
+        (kk x k, theta of length k: rbl_ritz_finish_cols)."""
         n, r0, r1, _ = self.matrix_info()
         Y = np.asfortranarray(Y, dtype=np.float64)
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         k = theta.size
-        if Y.shape != (k, k):
-            raise ValueError("ritz_finish: Y must be k x k and theta of length k")
+        if Y.ndim != 2 or Y.shape[1] != k or Y.shape[0] < k:
+            raise ValueError("ritz_finish: Y must be kk x k (kk >= k) and theta of length k")
         V = np.zeros((r1 - r0, k), order="F")
         res = np.zeros(k)
-        self._check(lib.rbl_ritz_finish(self._h, k, dptr(Y), dptr(theta), dptr(V), dptr(res)),
-                    "rbl_ritz_finish")
+        if Y.shape[0] == k:
+            self._check(lib.rbl_ritz_finish(self._h, k, dptr(Y), dptr(theta), dptr(V), dptr(res)),
+                        "rbl_ritz_finish")
+        else:
+            self._check(lib.rbl_ritz_finish_cols(self._h, Y.shape[0], k, dptr(Y), dptr(theta), dptr(V),
+                                                 dptr(res)), "rbl_ritz_finish_cols")
         return V, res
 
     def timers(self) -> dict:

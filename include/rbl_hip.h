@@ -354,9 +354,26 @@ int rbl_num_blocks(rbl_ctx* ctx);
  * only (rbl_start with basis_bits = 32 while a filter is set); no rectangular B; degree >= 0;
  * lo < hi; ref outside [lo, hi]; finite arguments. */
 int rbl_set_filter(rbl_ctx* ctx, int degree, double lo, double hi, double ref);
+/* rbl_set_filter_series: the Krylov operator becomes a general Chebyshev series
+ *     p(A) = sum_{j=0..degree} mu[j] T_j((A - c I) / e),   c = (lo + hi) / 2,  e = (hi - lo) / 2,
+ * with [lo, hi] enclosing the WHOLE spectrum of A (T_j grows exponentially outside it) — an
+ * operator that can peak inside the spectrum (rbl.interior: the eigenpairs nearest a target).
+ * Applied by T_0 = X, T_1 = (A X - c X) / e, T_j = (2 / e)(A T_{j-1} - c T_{j-1}) - T_{j-2}: each
+ * term one SpMM and one fused row pass that forms T_j and adds mu[j] T_j to the result, through
+ * three work blocks.  mu has degree + 1 entries and is copied.  Setting either kind of filter
+ * replaces the other; rbl_set_filter(ctx, 0, ...) clears both.  rbl_apply_filter, rbl_start,
+ * rbl_step and rbl_step_async apply whichever is set; rbl_apply stays the plain A X.
+ * Limits (RBL_ERR_INVALID, the context stays usable): 1 <= degree <= 65535; lo < hi, both finite;
+ * mu non-NULL, every entry finite; one rank only; the fp64 basis only (also rbl_start with
+ * basis_bits = 32 while the series is set); no rectangular B. */
+int rbl_set_filter_series(rbl_ctx* ctx, int degree, double lo, double hi, const double* mu);
 /* Y = p(A) X for a host n_local x b column-major block (the convention of rbl_apply), with the
  * filter set; RBL_ERR_STATE without one.  Timed under "AQ". */
 int rbl_apply_filter(rbl_ctx* ctx, int b, const double* X, double* Y);
+/* Diagnostics: the time per pass (ms, hipEvents, mean over `reps` after one warm-up) of the fused
+ * row pass of a series term and of the two plain row passes it replaces (the term, then the
+ * accumulation), each over blocks of `len` doubles allocated for the call. */
+int rbl_bench_series_pass(rbl_ctx* ctx, int64_t len, int reps, double* fused_ms, double* pair_ms);
 /* Rayleigh-Ritz on A with true residuals (also without a filter).
  * rbl_ritz_project: V = [Q_1..Q_nblocks] S (S: (nblocks*b) x k column-major, host; orthonormal
  *   columns) and W = A V (the plain operator) are formed and kept on the device; H_out (k x k
@@ -369,6 +386,11 @@ int rbl_apply_filter(rbl_ctx* ctx, int b, const double* X, double* Y);
 int rbl_ritz_project(rbl_ctx* ctx, int nblocks, int k, const double* S, double* H_out);
 int rbl_ritz_finish(rbl_ctx* ctx, int k, const double* Y, const double* theta, double* V_out,
                     double* resid_out);
+/* rbl_ritz_finish for a subset of the pairs: after rbl_ritz_project of width kproj, Y holds k <=
+ * kproj chosen eigenvector columns of H (kproj x k column-major) and theta their k eigenvalues;
+ * V_out is n_local x k and resid_out has k entries.  kproj == k is rbl_ritz_finish. */
+int rbl_ritz_finish_cols(rbl_ctx* ctx, int kproj, int k, const double* Y, const double* theta,
+                         double* V_out, double* resid_out);
 
 /* ---- restarted variants (restarted.jl: RBL_gpu_restarted / RBL_restarted) ---------------
  * Locked Ritz vectors live on the device (Qlock_gpu); fp64 basis runs only.

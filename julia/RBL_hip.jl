@@ -331,6 +331,58 @@ function RBL_hip_restarted(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k
     end
 end
 
+# One run of the loop (RBL_gpu.jl:134-203) on the operator the context holds (plain, rbl_set_filter or
+# rbl_set_filter_series), of at most m_cap steps, with the convergence test on the kc dominant
+# pairs when do_check: returns T, the last B, the steps run and whether it converged.
+function filtered_run(ctx::Ptr{Cvoid}, b::Int64, kc::Int64, seed::UInt64, kryl_sz::Int64,
+                      do_check::Bool, m_cap::Int64)
+    rbl_check(ctx, ccall((:rbl_start, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, UInt64),
+                         ctx, Cint(b), Cint(m_cap), Cint(64), C_NULL, seed), "rbl_start")
+    T = zeros(Float64, b + 1, 0)
+    Bl = zeros(Float64, b, b)
+    enqueued = 0
+    first = 1
+    i = 0
+    converged = false
+    while true
+        i += 1
+        is_check = do_check && i >= 2 && (i * b > kc) && (mod(i, 4) == 0)
+        is_last = !(i * b < kryl_sz && i < m_cap)
+        (is_check || is_last) || continue
+        while enqueued < i
+            enqueued += 1
+            part = (enqueued >= 2 && mod(enqueued, 2) == 0) ? 1 : 0
+            rbl_check(ctx, ccall((:rbl_step_async, librbl_hip), Cint, (Ptr{Cvoid}, Cint, Cint),
+                                 ctx, Cint(enqueued), Cint(part)), "rbl_step_async")
+        end
+        m = i + 1 - first
+        Ah = zeros(Float64, b, b, m)
+        Bh = zeros(Float64, b, b, m)
+        sts = zeros(Cint, m)
+        rbl_check(ctx, ccall((:rbl_fetch, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
+                             ctx, Cint(first), Cint(i + 1), Ah, Bh, sts), "rbl_fetch")
+        for (jj, j) in enumerate(first:i)
+            Ai = Ah[:, :, jj]
+            Bl = Bh[:, :, jj]
+            T = j == 1 ? insertA!(Ai, b) : [T insertA!(Ai, b)]
+            if j == i && is_check
+                D, V = dsbev('V', 'L', T)
+                D, V = sort_eig_abs(D, V, kc)
+                if check_convergence(Bl, V, b, kc, 1e-7)
+                    converged = true
+                    break
+                end
+            end
+            (j < i || !is_last) && insertB!(Bl, T, b, j)
+        end
+        first = i + 1
+        (converged || is_last) && break
+    end
+    return T, Bl, i, converged
+end
+
 # The k algebraically smallest (which = :SA) or largest (:LA) eigenpairs — eigsh's `which` —
 # through a Chebyshev filter (rbl_set_filter; no reference equivalent: RBL_gpu returns the
 # largest-magnitude pairs).  The same call sequence as rbl/filtered.py lanczos_filtered:
@@ -352,66 +404,18 @@ function RBL_gpu_filtered(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k:
         rbl_check(ctx, ccall((:rbl_set_filter, librbl_hip), Cint,
                              (Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble),
                              ctx, Cint(d), lo, hi, ref), "rbl_set_filter")
-    # one run of the loop (RBL_gpu.jl:134-203) of at most m_cap steps: T, the last B, steps
-    function run(do_check::Bool, m_cap::Int64)
-        rbl_check(ctx, ccall((:rbl_start, librbl_hip), Cint,
-                             (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, UInt64),
-                             ctx, Cint(b), Cint(m_cap), Cint(64), C_NULL, seed), "rbl_start")
-        T = zeros(Float64, b + 1, 0)
-        Bl = zeros(Float64, b, b)
-        enqueued = 0
-        first = 1
-        i = 0
-        converged = false
-        while true
-            i += 1
-            is_check = do_check && i >= 2 && (i * b > k) && (mod(i, 4) == 0)
-            is_last = !(i * b < kryl_sz && i < m_cap)
-            (is_check || is_last) || continue
-            while enqueued < i
-                enqueued += 1
-                part = (enqueued >= 2 && mod(enqueued, 2) == 0) ? 1 : 0
-                rbl_check(ctx, ccall((:rbl_step_async, librbl_hip), Cint, (Ptr{Cvoid}, Cint, Cint),
-                                     ctx, Cint(enqueued), Cint(part)), "rbl_step_async")
-            end
-            m = i + 1 - first
-            Ah = zeros(Float64, b, b, m)
-            Bh = zeros(Float64, b, b, m)
-            sts = zeros(Cint, m)
-            rbl_check(ctx, ccall((:rbl_fetch, librbl_hip), Cint,
-                                 (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
-                                 ctx, Cint(first), Cint(i + 1), Ah, Bh, sts), "rbl_fetch")
-            for (jj, j) in enumerate(first:i)
-                Ai = Ah[:, :, jj]
-                Bl = Bh[:, :, jj]
-                T = j == 1 ? insertA!(Ai, b) : [T insertA!(Ai, b)]
-                if j == i && is_check
-                    D, V = dsbev('V', 'L', T)
-                    D, V = sort_eig_abs(D, V, k)
-                    if check_convergence(Bl, V, b, k, 1e-7)
-                        converged = true
-                        break
-                    end
-                end
-                (j < i || !is_last) && insertB!(Bl, T, b, j)
-            end
-            first = i + 1
-            (converged || is_last) && break
-        end
-        return T, Bl, i, converged
-    end
     try
         set_matrix!(ctx, A)
         set_filter!(0, 0.0, 0.0, 0.0)
         s0 = max(1, min(max(8, cld(3 * k, b)), n ÷ b))
-        T0, B0, _, _ = run(false, s0)
+        T0, B0, _, _ = filtered_run(ctx, b, k, seed, kryl_sz, false, s0)
         w, Z = dsbev('V', 'L', T0)                                 # ascending
         res = [norm(B0 * Z[end-b+1:end, j]) for j in 1:length(w)]
         length(w) >= k + b || throw(RblError(-1, "RBL_gpu_filtered: fewer than k + b Ritz values"))
         lo, hi, ref = which == :SA ? (w[k+b], w[end] + res[end], w[1]) :
                                      (w[1] - res[1], w[end-(k+b)+1], w[end])
         set_filter!(degree, lo, hi, ref)
-        T, _, m, converged = run(true, cld(kryl_sz, b))
+        T, _, m, converged = filtered_run(ctx, b, k, seed, kryl_sz, true, cld(kryl_sz, b))
         converged || @warn "RBL_gpu_filtered: not converged within kryl_sz=$kryl_sz (best effort)"
         w, Z = dsbev('V', 'L', T)
         w, Z = sort_eig_abs(w, Z, k)                               # the dominant pairs of p(A)
@@ -438,6 +442,83 @@ function RBL_gpu_filtered(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k:
                              ctx, Cint(k), Y, theta, Vout, resid), "rbl_ritz_finish")
         set_filter!(0, 0.0, 0.0, 0.0)
         any(lo .<= theta .<= hi) && @warn "RBL_gpu_filtered: an eigenvalue returned lies in the damped interval"
+        return theta, Vout, resid
+    finally
+        ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
+    end
+end
+
+# The k eigenpairs nearest a target sigma — eigsh's `sigma` — through a Chebyshev series
+# (rbl_set_filter_series; no reference equivalent).  The same call sequence as rbl/interior.py
+# lanczos_interior:
+#   1. s0 = max(8, cld(3k, b)) plain block steps; the extreme Ritz values of T, their residual
+#      bounds and a pad of 1 % of their span give [lo, hi] enclosing the whole spectrum;
+#   2. mu = the Jackson-damped expansion of a delta at sigma scaled to p(sigma) = 1,
+#      rbl_set_filter_series, then the reference's loop and convergence test on the filtered T
+#      for kk = min(k + b, n) pairs;
+#   3. Rayleigh-Ritz on A over those kk vectors: rbl_ritz_project, the host solves
+#      H = Y Theta Y^T and keeps the k Ritz values nearest sigma (ascending),
+#      rbl_ritz_finish_cols returns V Y and the true residuals for those columns.
+# Returns D (ascending), V (n x k) and the residual norms.  One GPU, fp64 basis.
+function RBL_gpu_interior(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k::Int64, b::Int64,
+                          sigma::Float64; degree::Int = 100, device::Int = 0,
+                          seed::UInt64 = rand(UInt64), kryl_sz::Int64 = 1200)
+    degree >= 1 || throw(ArgumentError("degree must be >= 1"))
+    n = size(A, 2)
+    kk = min(k + b, n)
+    ctx = rbl_context(device)
+    clear_filter!() =
+        rbl_check(ctx, ccall((:rbl_set_filter, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble),
+                             ctx, Cint(0), 0.0, 0.0, 0.0), "rbl_set_filter")
+    try
+        set_matrix!(ctx, A)
+        clear_filter!()
+        s0 = max(1, min(max(8, cld(3 * k, b)), n ÷ b))
+        T0, B0, _, _ = filtered_run(ctx, b, k, seed, kryl_sz, false, s0)
+        w, Z = dsbev('V', 'L', T0)                                 # ascending
+        span = w[end] - w[1]
+        lo = w[1] - norm(B0 * Z[end-b+1:end, 1]) - 0.01 * span
+        hi = w[end] + norm(B0 * Z[end-b+1:end, end]) + 0.01 * span
+        lo < sigma < hi || throw(ArgumentError("sigma must lie inside the spectrum bounds ($lo, $hi)"))
+        c, e = (lo + hi) / 2, (hi - lo) / 2
+        ts = acos((sigma - c) / e)
+        a = pi / (degree + 2)
+        js = collect(0.0:1.0:Float64(degree))
+        g = ((1.0 .- js ./ (degree + 2)) .* sin(a) .* cos.(js .* a) .+
+             (1.0 / (degree + 2)) .* cos(a) .* sin.(js .* a)) ./ sin(a)
+        cs = cos.(js .* ts)
+        mu = g .* cs
+        mu[2:end] .*= 2.0
+        mu ./= dot(mu, cs)                                         # p(sigma) = 1
+        rbl_check(ctx, ccall((:rbl_set_filter_series, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cdouble, Cdouble, Ptr{Float64}),
+                             ctx, Cint(degree), lo, hi, mu), "rbl_set_filter_series")
+        T, _, m, converged = filtered_run(ctx, b, kk, seed, kryl_sz, true, cld(kryl_sz, b))
+        converged || @warn "RBL_gpu_interior: not converged within kryl_sz=$kryl_sz (best effort)"
+        w, Z = dsbev('V', 'L', T)
+        kp = min(kk, size(Z, 2))
+        w, Z = sort_eig_abs(w, Z, kp)                              # the dominant pairs of p(A)
+        S = Matrix{Float64}(Z[:, end:-1:1])
+        for col in 1:size(S, 2)
+            p = argmax(abs.(S[:, col]))
+            S[p, col] < 0 && (S[:, col] .*= -1)
+        end
+        H = zeros(Float64, kp, kp)
+        rbl_check(ctx, ccall((:rbl_ritz_project, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}),
+                             ctx, Cint(m), Cint(kp), S, H), "rbl_ritz_project")
+        F = eigen(Symmetric((H + H') / 2))                         # ascending
+        kept = min(k, kp)
+        sel = sort(sortperm(abs.(F.values .- sigma), alg = MergeSort)[1:kept])
+        theta = Vector{Float64}(F.values[sel])
+        Y = Matrix{Float64}(F.vectors[:, sel])
+        Vout = zeros(Float64, n, kept)
+        resid = zeros(Float64, kept)
+        rbl_check(ctx, ccall((:rbl_ritz_finish_cols, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                             ctx, Cint(kp), Cint(kept), Y, theta, Vout, resid), "rbl_ritz_finish_cols")
+        clear_filter!()
         return theta, Vout, resid
     finally
         ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)

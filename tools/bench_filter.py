@@ -18,6 +18,10 @@ Per-term cost (hipEvents, the library's "AQ" stage timer): rbl_apply_filter at d
 rbl_start plus step 1 (A * Omega and A * Q_1: no 3-term epilogue), halved.  The row pass of a term j >= 2
 reads three n x b blocks and writes one: 4 n b 8 bytes (term 1: 3 n b 8).
 
+--series times the Chebyshev series operator of rbl.RBL_interior instead: the fused row pass of a
+term against the two plain passes it replaces at a stream size that spills the caches, and one
+filtered block step (bench_series; default output profiles/series_bench.json).
+
 Writes one JSON document (default profiles/filter_bench.json)."""
 import argparse
 import json
@@ -126,8 +130,68 @@ def bench_matrix(rbl, name, gen, args):
     return out
 
 
+def bench_series(rbl, args):
+    """--series: the fused row pass of a Chebyshev series term (rbl_set_filter_series) against the
+    two cheb_axpby passes it replaces, on blocks of n * b doubles (default 2^21 x 32: 512 MiB a
+    block, four blocks — far past the caches), and one filtered block step of the interior run at
+    --series-degree on the band matrix (wall time of enqueued steps, and its "AQ" share)."""
+    from rbl import _lib
+    n, b = args.n_series, args.b
+    out = {"n": n, "b": b, "len": n * b, "repeats": args.repeats, "passes": args.series_passes}
+    with rbl.Context(0) as ctx:
+        fused, pair = [], []
+        f, p = np.zeros(1), np.zeros(1)
+        for rep in range(-1, args.repeats):             # rep -1: warm-up, not recorded
+            ctx._check(_lib.lib.rbl_bench_series_pass(ctx._h, n * b, args.series_passes, _lib.dptr(f),
+                                                      _lib.dptr(p)),
+                       "rbl_bench_series_pass")
+            if rep >= 0:
+                fused.append(float(f[0]))
+                pair.append(float(p[0]))
+            print(f"series pass rep {rep}: fused {f[0]:.4f} ms, pair {p[0]:.4f} ms", flush=True)
+        fm, pm = statistics.median(fused), statistics.median(pair)
+        out["pass"] = {"fused_ms": _stats(fused), "pair_ms": _stats(pair), "ratio": fm / pm,
+                       "fused_bytes": 6 * n * b * 8, "pair_bytes": 7 * n * b * 8,
+                       "model_ratio": 6.0 / 7.0,
+                       "fused_GBps": 6 * n * b * 8 / fm / 1e6, "pair_GBps": 7 * n * b * 8 / pm / 1e6}
+        print(f"series pass: {out['pass']}", flush=True)
+        # one filtered block step
+        ctx.gen_hashwindow(args.n_band, 64, 0.78, 20261015)
+        nb = ctx.matrix_info()[0]
+        (lo, hi), est = rbl.estimate_spectrum(ctx, args.k, b, seed=args.seed)
+        d = args.series_degree
+        sigma = 0.5 * (lo + hi) + 0.3 * 0.5 * (hi - lo)
+        ctx.set_filter_series(lo, hi, rbl.delta_coeffs(d, lo, hi, sigma))
+        steps, ts, aq = 4, [], []
+        ctx.set_option(_lib.RBL_OPT_TIMERS, 2)
+        for rep in range(-1, args.repeats):
+            ctx.start(b, steps + 1, seed=args.seed)
+            ctx.synchronize()
+            ctx.reset_timers()
+            t0 = time.perf_counter()
+            for i in range(1, steps + 1):
+                ctx.step_async(i, i >= 2 and i % 2 == 0)
+            ctx.fetch(1, steps + 1)
+            dt = (time.perf_counter() - t0) * 1e3 / steps
+            if rep >= 0:
+                ts.append(dt)
+                aq.append(ctx.timers()["AQ"] / steps)
+        ctx.set_option(_lib.RBL_OPT_TIMERS, 0)
+        ctx.set_filter(0)
+        out["step"] = {"matrix": "band", "n": nb, "degree": d, "lo": lo, "hi": hi, "sigma": sigma,
+                       "spmm_kernel": ctx.spmm_kernel_for(b), "step_ms": _stats(ts),
+                       "aq_ms": _stats(aq), "term_ms": statistics.median(aq) / d}
+        print(f"series step: {out['step']}", flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--series", action="store_true",
+                    help="time the Chebyshev series operator instead (see bench_series)")
+    ap.add_argument("--n-series", type=int, default=1 << 21)
+    ap.add_argument("--series-degree", type=int, default=100)
+    ap.add_argument("--series-passes", type=int, default=100, help="passes per timed window")
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--b", type=int, default=32)
     ap.add_argument("--degrees", type=int, nargs="+", default=[4, 8, 16])
@@ -140,6 +204,16 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "filter_bench.json"))
     args = ap.parse_args()
     import rbl
+    if args.series:
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(ROOT, "profiles", "series_bench.json")
+        doc = {"tool": "tools/bench_filter.py --series", "results": bench_series(rbl, args)}
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(json.dumps({"wrote": args.out}))
+        return
     gens = {"circuit": lambda c: c.gen_circuit(args.n_circuit),
             "band": lambda c: c.gen_hashwindow(args.n_band, 64, 0.78, 20261015)}
     doc = {"tool": "tools/bench_filter.py", "which": "SA", "results": []}
