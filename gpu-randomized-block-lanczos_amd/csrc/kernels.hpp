@@ -306,6 +306,16 @@ void cheb_axpby(int64_t len, const double* W, const double* Y, const double* Z, 
 void cheb_series_term(int64_t len, const double* W, const double* T1, const double* T2, double alpha,
                       double beta, double mu, double mu0, double* Tout, double* ACC, bool first,
                       bool last, hipStream_t s);
+// One term of the Chebyshev moments after its SpMM W = A t_{j-1} (n x b row-major blocks):
+//   t_j = alpha W + beta T1 (- T2 unless first), stored to Tout unless last (Tout may be W), and
+//   part[g][q][c], g < grid = moment_grid(nrows, b), c < b: workgroup g's partial column sums
+//   q = 0: <t_j,t_j>, q = 1: <t_j,T1>, and if first q = 2: <T1,T1>  (2b or 3b doubles per g).
+// A fixed summation order, no atomics; reduce_slab over the grid gives the dots.  16-byte
+// accesses when b is even and every pointer used is 16-byte aligned, else 8-byte.
+int moment_grid(int64_t nrows, int b);
+void cheb_moment_term(int64_t nrows, int b, const double* W, const double* T1, const double* T2,
+                      double alpha, double beta, double* Tout, double* part, int grid, bool first,
+                      bool last, hipStream_t s);
 // part[g][c] = sum over workgroup g's rows of (Z[r][c] - X[r][c] theta[c])^2, c < kp (Z, X: n x kp
 // row-major), g < grid = resid_grid(nrows): a fixed summation order, no atomics; reduce_slab
 // over the grid gives the squared column norms.

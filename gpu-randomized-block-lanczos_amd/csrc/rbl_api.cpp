@@ -4194,6 +4194,129 @@ int rbl_bench_series_pass(rbl_ctx* ctx, int64_t len, int reps, double* fused_ms,
   return RBL_OK;
 }
 
+// ---- Chebyshev moments (kernel polynomial method) ------------------------------------------
+// m_j = x_c^T T_j((A - cI)/e) x_c, j = 0..2 degree, from degree SpMMs: t_j = T_j x by the
+// recurrence and scalars of series_apply, and the product identities
+//     m_0 = <x,x>,  m_1 = <t_1,x>,  m_{2j} = 2 <t_j,t_j> - m_0,  m_{2j-1} = 2 <t_j,t_{j-1}> - m_1.
+// The blocks are the call's own: t_j lives in buf[j % 3] with x = t_0 in buf[0]; term j's SpMM
+// writes W = A t_{j-1} over t_{j-3} (dead by then) and cheb_moment_term turns W into t_j in place
+// while it forms the partials of the two dots, which reduce_slab adds into the term's slot of
+// `dots` (term 1: [tt, tp, xx], 3b; term j >= 2: [tt, tp], 2b).  One D2H at the end; the doubling
+// finishes here in float64.
+int rbl_cheb_moments(rbl_ctx* ctx, int b, int degree, double lo, double hi, const double* X,
+                     uint64_t seed, double* mom_out) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (b < 1 || b > RBL_MAX_BLOCK)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_moments: b must be in [1," + std::to_string(RBL_MAX_BLOCK) + "]");
+  if (degree < 1 || degree > 65535)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_moments: degree must be in [1, 65535]");
+  if (!std::isfinite(lo) || !std::isfinite(hi))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_moments: lo and hi must be finite");
+  if (!(lo < hi)) return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_moments: needs lo < hi");
+  if (!mom_out) return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_moments: mom_out is NULL");
+  if (ctx->nranks > 1)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_moments: one rank only (nranks > 1 is not supported)");
+  if (!has_matrix(ctx)) return fail(ctx, RBL_ERR_STATE, "rbl_cheb_moments: no matrix");
+  if (ctx->rect)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_moments: not with a rectangular B (rbl_set_matrix_normal)");
+  HIPC(hipSetDevice(ctx->device));
+  const int64_t n = ctx->nloc, nl = std::max<int64_t>(n, 1);
+  const size_t padded = (size_t)(nl + kRowPad) * b * sizeof(double);
+  const size_t nmom = (size_t)(2 * degree + 1) * b;
+  const int grid = moment_grid(n, b);
+  DevBuf f[3], slab, dots;
+  for (DevBuf& p : f) {
+    HIPC(hipMalloc(&p.p, padded));
+    HIPC(hipMemsetAsync(p.p, 0, padded, ctx->stream));
+  }
+  HIPC(hipMalloc(&slab.p, (size_t)grid * 3 * b * sizeof(double)));
+  HIPC(hipMalloc(&dots.p, nmom * sizeof(double)));
+  if (X) {  // column-major through f[1], which the first SpMM overwrites
+    HIPC(hipMemcpyAsync(f[1].p, X, n * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    colmajor_to_rowmajor(f[1].d(), n, b, f[0].d(), ctx->stream);
+  } else {
+    randn_block(f[0].d(), n, b, ctx->r0, seed, ctx->stream, ctx->relabeled ? &ctx->relabel_perm : nullptr);
+  }
+  HIPC(hipGetLastError());
+  const double c = 0.5 * (lo + hi), e = 0.5 * (hi - lo);
+  {
+    StageScope t(ctx, RBL_STAGE_AQ);
+    const double* t1 = f[0].d();  // t_{j-1}
+    const double* t2 = nullptr;   // t_{j-2}
+    double* dj = dots.d();
+    for (int j = 1; j <= degree; ++j) {
+      double* tj = f[j % 3].d();
+      const int st = apply_A(ctx, t1, 0, b, tj, nullptr, nullptr, nullptr);
+      if (st < 0) return st;
+      const double al = (j == 1 ? 1.0 : 2.0) / e;
+      const int nq = j == 1 ? 3 : 2;
+      cheb_moment_term(n, b, tj, t1, t2, al, -al * c, tj, slab.d(), grid, j == 1, j == degree, ctx->stream);
+      reduce_slab(slab.d(), grid, (int64_t)nq * b, dj, nullptr, ctx->stream);
+      HIPC(hipGetLastError());
+      dj += (size_t)nq * b;
+      t2 = t1;
+      t1 = tj;
+    }
+  }
+  std::vector<double> d(nmom);
+  HIPC(hipMemcpyAsync(d.data(), dots.p, nmom * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  harvest_timers(ctx);
+  const size_t ld = (size_t)2 * degree + 1;
+  for (int col = 0; col < b; ++col) {
+    double* m = mom_out + ld * col;
+    const double m0 = d[(size_t)2 * b + col], m1 = d[(size_t)b + col];
+    m[0] = m0;
+    m[1] = m1;
+    m[2] = 2.0 * d[col] - m0;
+    for (int j = 2; j <= degree; ++j) {
+      const double* dj = d.data() + (size_t)3 * b + (size_t)(j - 2) * 2 * b;
+      m[2 * j] = 2.0 * dj[col] - m0;
+      m[2 * j - 1] = 2.0 * dj[b + col] - m1;
+    }
+  }
+  return RBL_OK;
+}
+
+// Diagnostics (tools/bench_filter.py --moments): hipEvent time per pass of the moment pass (a
+// middle term: reads W, t_{j-1}, t_{j-2}; writes t_j over W and the workgroup partials), its
+// reduce_slab included, on blocks of len_rows x b doubles.  The coefficients keep the values
+// bounded over any number of repeats.
+int rbl_bench_moment_pass(rbl_ctx* ctx, int64_t len_rows, int b, int reps, double* ms) {
+  if (!ctx || len_rows < 1 || b < 1 || b > RBL_MAX_BLOCK || reps < 1 || !ms)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_moment_pass: bad arguments");
+  HIPC(hipSetDevice(ctx->device));
+  const int grid = moment_grid(len_rows, b);
+  DevBuf w, t1, t2, slab, dots;
+  const size_t bytes = (size_t)len_rows * b * sizeof(double);
+  for (DevBuf* p : {&w, &t1, &t2}) {
+    HIPC(hipMalloc(&p->p, bytes));
+    HIPC(hipMemsetAsync(p->p, 0, bytes, ctx->stream));
+  }
+  HIPC(hipMalloc(&slab.p, (size_t)grid * 2 * b * sizeof(double)));
+  HIPC(hipMalloc(&dots.p, (size_t)2 * b * sizeof(double)));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  auto pass = [&] {
+    cheb_moment_term(len_rows, b, w.d(), t1.d(), t2.d(), 0.5, 0.25, w.d(), slab.d(), grid, false, false,
+                     ctx->stream);
+    reduce_slab(slab.d(), grid, (int64_t)2 * b, dots.d(), nullptr, ctx->stream);
+  };
+  int st = RBL_OK;
+  pass();  // warm-up
+  if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+  for (int r = 0; r < reps; ++r) pass();
+  if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+  float el = 0.f;
+  if (hipEventElapsedTime(&el, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+  *ms = (double)el / reps;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_moment_pass: a HIP call failed");
+  return RBL_OK;
+}
+
 // ---- Rayleigh-Ritz on A -------------------------------------------------------------------
 int rbl_ritz_project(rbl_ctx* ctx, int nblocks, int k, const double* S, double* H_out) {
   if (!ctx || nblocks < 1 || k < 1 || !S || !H_out)

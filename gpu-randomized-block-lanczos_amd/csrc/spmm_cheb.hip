@@ -20,6 +20,11 @@
 // T_{j-2}, ACC; T_j, ACC) against the 5 + 2 of cheb_axpby followed by a second cheb_axpby as
 // the accumulate, and one launch instead of two.
 //
+// cheb_moment_term is the row pass of the Chebyshev moments x^T T_j((A - cI)/e) x
+// (rbl_cheb_moments): the same unscaled term, and in the same sweep the per-column partial sums
+// of <t_j,t_j> and <t_j,t_{j-1}> — 3 reads + 1 write per element, no second sweep for the dots,
+// the sums in the fixed order of resid_partial.
+//
 // resid_partial forms the per-workgroup partials of the column sums of (Z - X diag(theta))^2 —
 // the true residuals ||A v - theta v||^2 of rbl_ritz_finish — summed in a fixed order (each
 // thread over its rows ascending, then the workgroup's row groups ascending in LDS; reduce_slab
@@ -167,6 +172,90 @@ __global__ __launch_bounds__(kChebThreads) void k_resid_partial(int64_t nrows, i
   }
 }
 
+// One term of the moment recurrence (rbl_cheb_moments) after its SpMM W = A t_{j-1}:
+//     t_j = alpha W + beta t_{j-1} (- t_{j-2}),   stored to Tout unless LAST (Tout may be W),
+// and the workgroup's partials of the column sums <t_j,t_j>, <t_j,t_{j-1}> and, FIRST (j = 1:
+// t_{j-1} = x, no t_{j-2}), <x,x>:  part[g][q][c], q < NQ = 2 (3 if FIRST), c < b.
+// A row of the n x b row-major blocks is cw slots of type T (d2v: cw = b / 2 column pairs, double:
+// cw = b columns), so a thread keeps its slot's columns for the whole pass.  The workgroup covers
+// a tile of nrg = 256 / cw rows at a time (thread t reads slot t of the tile: one contiguous
+// stream per workgroup) and the tiles are walked grid-stride; a row wider than 256 slots is
+// covered in chunks of 256, one after the other.  The sums keep a fixed order, as
+// k_resid_partial's: each thread over its rows ascending, then the row groups ascending in LDS;
+// reduce_slab adds the workgroups in order.  No atomics.
+template <typename T>
+__device__ __forceinline__ void moment_stage(double* sm, int q, T v);
+template <>
+__device__ __forceinline__ void moment_stage<double>(double* sm, int q, double v) {
+  sm[q * kChebThreads + threadIdx.x] = v;
+}
+template <>
+__device__ __forceinline__ void moment_stage<d2v>(double* sm, int q, d2v v) {
+  sm[(2 * q) * kChebThreads + threadIdx.x] = v.x;
+  sm[(2 * q + 1) * kChebThreads + threadIdx.x] = v.y;
+}
+
+template <typename T, bool FIRST, bool LAST>
+__global__ __launch_bounds__(kChebThreads) void k_cheb_moment(int64_t nrows, int cw, const T* W,
+                                                              const T* __restrict__ T1,
+                                                              const T* __restrict__ T2, double alpha,
+                                                              double beta, T* Tout,
+                                                              double* __restrict__ part) {
+  constexpr int VW = sizeof(T) / sizeof(double);  // columns per slot
+  constexpr int NQ = FIRST ? 3 : 2;
+  __shared__ double sm[NQ * VW * kChebThreads];
+  const int cwl = cw < kChebThreads ? cw : kChebThreads;  // slots of a row covered at once
+  const int nrg = kChebThreads / cwl;                     // rows per tile
+  const int rg = threadIdx.x / cwl, cl = threadIdx.x % cwl;
+  const int64_t rstride = (int64_t)gridDim.x * nrg;
+  double* out = part + (int64_t)blockIdx.x * NQ * VW * cw;
+  for (int cb = 0; cb < cw; cb += cwl) {
+    const int c = cb + cl;
+    T tt = T(0.0), tp = T(0.0), xx = T(0.0);
+    if (rg < nrg && c < cw) {
+      for (int64_t r = (int64_t)blockIdx.x * nrg + rg; r < nrows; r += rstride) {
+        const int64_t i = r * cw + c;
+        const T t1 = T1[i];
+        T t = alpha * W[i] + beta * t1;
+        if constexpr (FIRST) xx += t1 * t1;
+        else t -= T2[i];
+        tt += t * t;
+        tp += t * t1;
+        if constexpr (!LAST) Tout[i] = t;
+      }
+    }
+    moment_stage<T>(sm, 0, tt);
+    moment_stage<T>(sm, 1, tp);
+    if constexpr (FIRST) moment_stage<T>(sm, 2, xx);
+    __syncthreads();
+    const int ncl = cw - cb < cwl ? cw - cb : cwl;  // slots of this chunk
+    for (int idx = threadIdx.x; idx < NQ * VW * ncl; idx += kChebThreads) {
+      const int qv = idx / ncl, c2 = idx % ncl;  // qv = q * VW + lane of the slot
+      double s = 0.0;
+      for (int g = 0; g < nrg; ++g) s += sm[qv * kChebThreads + g * cwl + c2];
+      out[(qv / VW) * (VW * cw) + (cb + c2) * VW + qv % VW] = s;
+    }
+    __syncthreads();
+  }
+}
+
+template <typename T>
+void launch_cheb_moment(int grid, int64_t nrows, int cw, const double* W, const double* T1,
+                        const double* T2, double alpha, double beta, double* Tout, double* part,
+                        bool first, bool last, hipStream_t s) {
+  const T *w = reinterpret_cast<const T*>(W), *t1 = reinterpret_cast<const T*>(T1),
+          *t2 = reinterpret_cast<const T*>(T2);
+  T* to = reinterpret_cast<T*>(Tout);
+#define RBL_MOMENT_LAUNCH(F, L)                                                                   \
+  hipLaunchKernelGGL((k_cheb_moment<T, F, L>), dim3(grid), dim3(kChebThreads), 0, s, nrows, cw, w, \
+                     t1, t2, alpha, beta, to, part)
+  if (first && last) RBL_MOMENT_LAUNCH(true, true);
+  else if (first) RBL_MOMENT_LAUNCH(true, false);
+  else if (last) RBL_MOMENT_LAUNCH(false, true);
+  else RBL_MOMENT_LAUNCH(false, false);
+#undef RBL_MOMENT_LAUNCH
+}
+
 __global__ __launch_bounds__(kChebThreads) void k_copy_cols(int64_t nrows, int w, const double* __restrict__ src,
                                                             int lds, int s0, double* __restrict__ dst,
                                                             int ldd, int d0) {
@@ -228,6 +317,23 @@ void cheb_series_term(int64_t len, const double* W, const double* T1, const doub
   }
   launch_cheb_series<double>(stream_grid(len, kChebPerCu), len, (int64_t)-1, W, T1, T2, alpha, beta,
                              mu, mu0, Tout, ACC, first, last, s);
+}
+
+int moment_grid(int64_t nrows, int b) {
+  return stream_grid(nrows * ((b + 1) / 2), kChebPerCu);
+}
+
+void cheb_moment_term(int64_t nrows, int b, const double* W, const double* T1, const double* T2,
+                      double alpha, double beta, double* Tout, double* part, int grid, bool first,
+                      bool last, hipStream_t s) {
+  if (nrows <= 0 || b <= 0) return;
+  // a thread keeps a column pair only when every row starts on a pair: b even
+  const bool vec = b % 2 == 0 && aligned16(W) && aligned16(T1) && (first || aligned16(T2)) &&
+                   (last || aligned16(Tout));
+  if (vec)
+    launch_cheb_moment<d2v>(grid, nrows, b / 2, W, T1, T2, alpha, beta, Tout, part, first, last, s);
+  else
+    launch_cheb_moment<double>(grid, nrows, b, W, T1, T2, alpha, beta, Tout, part, first, last, s);
 }
 
 int resid_grid(int64_t nrows) {

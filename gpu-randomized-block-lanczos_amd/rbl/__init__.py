@@ -3,7 +3,8 @@
 ``RBL_gpu(A, k, b)`` mirrors Julia/RBL_gpu.jl:205, ``RBL_svd(B, k, b)`` the truncated SVD of
 images.jl:20-33 on the implicit B^T B, ``RBL_filtered(A, k, b, which="SA"|"LA")`` the smallest or
 largest eigenpairs through a Chebyshev filter, ``RBL_interior(A, k, b, sigma)`` the eigenpairs
-nearest sigma through a Chebyshev delta series; ``Context`` wraps the C-ABI of
+nearest sigma through a Chebyshev delta series, ``RBL_interval(A, (x0, x1), b)`` all eigenpairs in
+an interval (``spectral_density`` / ``eig_count``: the Chebyshev moments behind it); ``Context`` wraps the C-ABI of
 librbl_hip.so (include/rbl_hip.h).  Importing this package loads the HIP library and fails
 loudly if it has not been built: there is no CPU fallback.
 """
@@ -17,3 +18,5 @@ from .svd import RBL_svd  # noqa: F401
 from .filtered import RBL_filtered, cheb_scalars, filter_bounds, lanczos_filtered  # noqa: F401
 from .interior import (RBL_interior, delta_coeffs, estimate_spectrum, lanczos_interior,  # noqa: F401
                        series_eval, spectrum_bounds)
+from .density import (RBL_interval, check_moments, eig_count, interval_degree, interval_run,  # noqa: F401
+                      jackson, kpm_count, kpm_density, spectral_density)

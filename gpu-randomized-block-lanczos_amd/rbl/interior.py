@@ -38,6 +38,18 @@ HALF_WIDTH_C = 3.735
 P_MIN_FLOOR = 0.01
 
 
+def jackson(M: int) -> np.ndarray:
+    """The Jackson damping factors g_0..g_M of a degree-M Chebyshev expansion (g_0 = 1):
+        g_j = [(1 - j/(M+2)) sin(a) cos(j a) + (1/(M+2)) cos(a) sin(j a)] / sin(a),  a = pi/(M+2)."""
+    if M < 0:
+        raise ValueError("jackson: M must be >= 0")
+    d = int(M)
+    j = np.arange(d + 1, dtype=np.float64)
+    a = math.pi / (d + 2)
+    return ((1.0 - j / (d + 2)) * math.sin(a) * np.cos(j * a) + (1.0 / (d + 2)) * math.cos(a) * np.sin(j * a)) \
+        / math.sin(a)
+
+
 def delta_coeffs(degree: int, lo: float, hi: float, sigma: float) -> np.ndarray:
     """mu_0..mu_degree of the Jackson-damped Chebyshev expansion of a delta at sigma on [lo, hi]:
         mu_j = (2 - delta_j0) g_j cos(j theta_s),  theta_s = arccos((sigma - c) / e),
@@ -53,9 +65,7 @@ def delta_coeffs(degree: int, lo: float, hi: float, sigma: float) -> np.ndarray:
     c, e = 0.5 * (lo + hi), 0.5 * (hi - lo)
     ts = math.acos((sigma - c) / e)
     j = np.arange(d + 1, dtype=np.float64)
-    a = math.pi / (d + 2)
-    g = ((1.0 - j / (d + 2)) * math.sin(a) * np.cos(j * a) + (1.0 / (d + 2)) * math.cos(a) * np.sin(j * a)) \
-        / math.sin(a)
+    g = jackson(d)
     cs = np.cos(j * ts)
     mu = g * cs
     mu[1:] *= 2.0

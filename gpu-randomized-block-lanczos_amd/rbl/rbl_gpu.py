@@ -375,6 +375,24 @@ class Context:
         self._check(lib.rbl_apply_filter(self._h, X.shape[1], dptr(X), dptr(Y)), "rbl_apply_filter")
         return Y
 
+    def cheb_moments(self, b: int, degree: int, lo: float, hi: float, X=None, seed: int = 0) -> np.ndarray:
+        """rbl_cheb_moments: mom[j, c] = x_c^T T_j((A - cI)/e) x_c, j = 0..2 degree, shape
+        (2 degree + 1, b), from `degree` SpMMs.  [lo, hi] must enclose the whole spectrum.  X: n x b
+        host block, or None for the device's N(0,1) draw from `seed` (rbl.density turns the moments
+        into a spectral density and eigenvalue counts)."""
+        b, degree = int(b), int(degree)
+        xp = None
+        if X is not None:
+            n, r0, r1, _ = self.matrix_info()
+            X = np.asfortranarray(X, dtype=np.float64)
+            if X.ndim != 2 or X.shape != (r1 - r0, b):
+                raise ValueError(f"cheb_moments: X must be {r1 - r0} x {b}")
+            xp = dptr(X)
+        mom = np.zeros((max(2 * degree + 1, 1), max(b, 1)), order="F")
+        self._check(lib.rbl_cheb_moments(self._h, b, degree, float(lo), float(hi), xp, int(seed) & (2**64 - 1),
+                                         dptr(mom)), "rbl_cheb_moments")
+        return mom
+
     def ritz_project(self, nblocks: int, k: int, S: np.ndarray) -> np.ndarray:
         """rbl_ritz_project: V = [Q_1..Q_nblocks] S and W = A V stay on the device; returns
         H = V^T W (k x k)."""

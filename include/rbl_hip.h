@@ -374,6 +374,28 @@ int rbl_apply_filter(rbl_ctx* ctx, int b, const double* X, double* Y);
  * row pass of a series term and of the two plain row passes it replaces (the term, then the
  * accumulation), each over blocks of `len` doubles allocated for the call. */
 int rbl_bench_series_pass(rbl_ctx* ctx, int64_t len, int reps, double* fused_ms, double* pair_ms);
+/* rbl_cheb_moments: the Chebyshev moments of A over a block of b vectors (the kernel polynomial
+ * method: spectral density, eigenvalue counts; rbl.density),
+ *     mom_out[j + (2 degree + 1) c] = x_c^T T_j((A - cI) / e) x_c,   j = 0..2 degree,
+ * c = (lo + hi) / 2, e = (hi - lo) / 2, with [lo, hi] enclosing the WHOLE spectrum of A (|m_j| <=
+ * m_0 then; T_j grows exponentially outside it).  X: host n_local x b column-major, or NULL for
+ * the counter-based N(0,1) draw of rbl_start (the same seed gives the same block).  mom_out: host,
+ * (2 degree + 1) x b column-major.  degree SpMMs give 2 degree + 1 moments: with t_j = T_j x from
+ * the recurrence of rbl_set_filter_series,
+ *     m_0 = <x,x>,  m_1 = <t_1,x>,  m_2j = 2 <t_j,t_j> - m_0,  m_(2j-1) = 2 <t_j,t_(j-1)> - m_1,
+ * each term one SpMM and one row pass that forms t_j and the per-column partials of both dots
+ * (a fixed summation order, no atomics: two calls give the same bits).  The dots of all terms stay
+ * on the device until one copy at the end.  The call allocates its own three work blocks: the
+ * Krylov basis, a run in progress and a filter that is set are untouched.  Timed under "AQ".
+ * Limits (RBL_ERR_INVALID, before any allocation; the context stays usable): 1 <= b <=
+ * RBL_MAX_BLOCK; 1 <= degree <= 65535; lo < hi, both finite; mom_out non-NULL; one rank only; no
+ * rectangular B.  RBL_ERR_STATE without a matrix. */
+int rbl_cheb_moments(rbl_ctx* ctx, int b, int degree, double lo, double hi, const double* X,
+                     uint64_t seed, double* mom_out);
+/* Diagnostics: the time per pass (ms, hipEvents, mean over `reps` after one warm-up) of the moment
+ * row pass of a middle term with its partial-sum reduction, over blocks of len_rows x b doubles
+ * allocated for the call. */
+int rbl_bench_moment_pass(rbl_ctx* ctx, int64_t len_rows, int b, int reps, double* ms);
 /* Rayleigh-Ritz on A with true residuals (also without a filter).
  * rbl_ritz_project: V = [Q_1..Q_nblocks] S (S: (nblocks*b) x k column-major, host; orthonormal
  *   columns) and W = A V (the plain operator) are formed and kept on the device; H_out (k x k

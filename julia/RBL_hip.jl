@@ -17,6 +17,7 @@
 #   U, D, V = RBL_gpu_svd(B, k, b)       # images.jl:29-33 on a sparse rectangular B, B^T B implicit
 #   D, V, r = RBL_gpu_filtered(A, k, b; which = :SA, degree = 8)   # the k smallest (or :LA largest)
 #                                        # pairs through a Chebyshev filter, r = ||A v - D v||
+#   c, (lo, hi) = RBL_gpu_eigcount(A, x0, x1)     # expected number of eigenvalues in [x0, x1] (KPM)
 #
 # Untested here: Julia is not installed in the build container (SURVEY §8(c)).  Every ccall
 # below is checked against include/rbl_hip.h by tests/test_julia_binding.py (argument count
@@ -520,6 +521,78 @@ function RBL_gpu_interior(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k:
                              ctx, Cint(kp), Cint(kept), Y, theta, Vout, resid), "rbl_ritz_finish_cols")
         clear_filter!()
         return theta, Vout, resid
+    finally
+        ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
+    end
+end
+
+# The Chebyshev moments m[j+1, c] = x_c' T_j((A - cI)/e) x_c, j = 0..2 degree, of the matrix the
+# context holds (rbl_cheb_moments: `degree` SpMMs, each followed by one row pass that forms T_j x
+# and the two dot products that give two moments).  [lo, hi] must enclose the whole spectrum.
+# X: n x b Matrix{Float64}, or nothing for the device's N(0,1) draw from `seed`.
+function cheb_moments(ctx::Ptr{Cvoid}, b::Int64, degree::Int64, lo::Float64, hi::Float64;
+                      X::Union{Nothing,Matrix{Float64}} = nothing, seed::UInt64 = UInt64(0))
+    mom = zeros(Float64, 2 * degree + 1, b)
+    rbl_check(ctx, ccall((:rbl_cheb_moments, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Cint, Cint, Cdouble, Cdouble, Ptr{Float64}, UInt64, Ptr{Float64}),
+                         ctx, Cint(b), Cint(degree), lo, hi, X === nothing ? C_NULL : X, seed, mom),
+              "rbl_cheb_moments")
+    return mom
+end
+
+# The expected number of eigenvalues of A in [x0, x1] by the kernel polynomial method (no
+# reference equivalent).  The same call sequence and host arithmetic as rbl/density.py eig_count:
+#   1. 8 plain block steps of block min(16, n ÷ 8); the extreme Ritz values of T, their residual
+#      bounds and a pad of 1 % of their span give [lo, hi] enclosing the whole spectrum;
+#   2. cheb_moments over nvec device-drawn N(0,1) vectors: 2 degree + 1 moments, each bounded by
+#      m_0 when [lo, hi] does enclose the spectrum (checked; bounds that fall short are widened
+#      by 10 % of their width on both sides and the moments taken again, up to 3 times);
+#   3. count = sum_j g_j gamma_j mu_j with mu_j the mean of the moments over the vectors, g_j the
+#      Jackson factors and gamma_0 = (th0 - th1)/pi, gamma_j = 2 (sin j th0 - sin j th1)/(j pi),
+#      th = acos((x - c)/e): the damped step function of Di Napoli, Polizzi and Saad.  Its edges
+#      are about e pi / (2 degree + 2) wide.
+# Returns the count and (lo, hi).  One GPU.
+function RBL_gpu_eigcount(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, x0::Float64, x1::Float64;
+                          nvec::Int64 = 32, degree::Int64 = 100, device::Int = 0,
+                          seed::UInt64 = rand(UInt64), kryl_sz::Int64 = 1200)
+    x0 <= x1 || throw(ArgumentError("needs x0 <= x1"))
+    n = size(A, 2)
+    ctx = rbl_context(device)
+    try
+        set_matrix!(ctx, A)
+        rbl_check(ctx, ccall((:rbl_set_filter, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble),
+                             ctx, Cint(0), 0.0, 0.0, 0.0), "rbl_set_filter")
+        b = max(1, min(16, n ÷ 8))
+        s0 = max(1, min(max(8, cld(3 * b, b)), n ÷ b))
+        T0, B0, _, _ = filtered_run(ctx, b, b, seed, kryl_sz, false, s0)
+        w, Z = dsbev('V', 'L', T0)                                 # ascending
+        span = w[end] - w[1]
+        lo = w[1] - norm(B0 * Z[end-b+1:end, 1]) - 0.01 * span
+        hi = w[end] + norm(B0 * Z[end-b+1:end, end]) + 0.01 * span
+        mom = cheb_moments(ctx, nvec, degree, lo, hi; seed = seed)
+        encloses(m) = all(isfinite, m) && all(abs.(m) .<= (1 + 1e-8) .* m[1:1, :])
+        for _ in 1:3                                               # estimated bounds that fall short
+            encloses(mom) && break
+            wd = hi - lo
+            lo, hi = lo - 0.1 * wd, hi + 0.1 * wd
+            mom = cheb_moments(ctx, nvec, degree, lo, hi; seed = seed)
+        end
+        encloses(mom) ||
+            throw(RblError(-1, "RBL_gpu_eigcount: the bounds ($lo, $hi) do not enclose the spectrum"))
+        M = 2 * degree
+        c, e = (lo + hi) / 2, (hi - lo) / 2
+        th0 = acos(clamp((x0 - c) / e, -1.0, 1.0))
+        th1 = acos(clamp((x1 - c) / e, -1.0, 1.0))
+        a = pi / (M + 2)
+        js = collect(0.0:1.0:Float64(M))
+        g = ((1.0 .- js ./ (M + 2)) .* sin(a) .* cos.(js .* a) .+
+             (1.0 / (M + 2)) .* cos(a) .* sin.(js .* a)) ./ sin(a)
+        gamma = zeros(Float64, M + 1)
+        gamma[1] = (th0 - th1) / pi
+        gamma[2:end] = 2.0 .* (sin.(js[2:end] .* th0) .- sin.(js[2:end] .* th1)) ./ (js[2:end] .* pi)
+        mu = vec(sum(mom, dims = 2)) ./ nvec
+        return dot(g .* gamma, mu), (lo, hi)
     finally
         ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
     end

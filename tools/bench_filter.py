@@ -22,6 +22,10 @@ reads three n x b blocks and writes one: 4 n b 8 bytes (term 1: 3 n b 8).
 term against the two plain passes it replaces at a stream size that spills the caches, and one
 filtered block step (bench_series; default output profiles/series_bench.json).
 
+--moments times the Chebyshev moment pass of rbl_cheb_moments next to that fused series pass at
+the headline block, and one moments call against one plain block step (bench_moments; default
+output profiles/moments_bench.json).
+
 Writes one JSON document (default profiles/filter_bench.json)."""
 import argparse
 import json
@@ -185,8 +189,74 @@ def bench_series(rbl, args):
     return out
 
 
+def bench_moments(rbl, args):
+    """--moments: the moment row pass of rbl_cheb_moments (reads W, t_{j-1}, t_{j-2}, writes t_j:
+    4 n b 8 bytes, plus the partial-sum reduction) next to the fused series pass (6 n b 8 bytes)
+    on blocks of the same n * b doubles (default 1e7 x 32, the headline block), alternated in one
+    process; then the wall time of one moments call (nvec = b, --moments-degree terms) on the
+    headline band matrix against one plain block step of the same context."""
+    from rbl import _lib
+    n, b = args.n_moments, args.b
+    out = {"n": n, "b": b, "len": n * b, "repeats": args.repeats, "passes": args.series_passes}
+    with rbl.Context(0) as ctx:
+        mom, fused = [], []
+        m, f, p = np.zeros(1), np.zeros(1), np.zeros(1)
+        for rep in range(-1, args.repeats):             # rep -1: warm-up, not recorded
+            ctx._check(_lib.lib.rbl_bench_moment_pass(ctx._h, n, b, args.series_passes, _lib.dptr(m)),
+                       "rbl_bench_moment_pass")
+            ctx._check(_lib.lib.rbl_bench_series_pass(ctx._h, n * b, args.series_passes, _lib.dptr(f),
+                                                      _lib.dptr(p)), "rbl_bench_series_pass")
+            if rep >= 0:
+                mom.append(float(m[0]))
+                fused.append(float(f[0]))
+            print(f"moment pass rep {rep}: moment {m[0]:.4f} ms, fused_ms {f[0]:.4f} ms", flush=True)
+        mm, fm = statistics.median(mom), statistics.median(fused)
+        out["pass"] = {"moment_ms": _stats(mom), "fused_ms": _stats(fused), "ratio": mm / fm,
+                       "moment_bytes": 4 * n * b * 8, "fused_bytes": 6 * n * b * 8, "model_ratio": 4.0 / 6.0,
+                       "moment_GBps": 4 * n * b * 8 / mm / 1e6, "fused_GBps": 6 * n * b * 8 / fm / 1e6}
+        print(f"moment pass: {out['pass']}", flush=True)
+        # one moments call against one plain block step, on the headline matrix
+        ctx.gen_hashwindow(args.n_headline, 64, 0.7734, 20261015)
+        nb = ctx.matrix_info()[0]
+        from rbl import density
+        (lo0, hi0), est = rbl.estimate_spectrum(ctx, b, b, seed=args.seed)
+        d = args.moments_degree
+        # the 8-step estimate can stop short of the edge of a dense bulk: widened until the moments
+        # accept the bounds, as rbl.eig_count does (not timed)
+        _, (lo, hi) = density.checked_moments(ctx, b, d, lo0, hi0, args.seed, True)
+        steps, ts, tm = 4, [], []
+        for rep in range(-1, args.repeats):
+            t0 = time.perf_counter()
+            mo = ctx.cheb_moments(b, d, lo, hi, None, args.seed)
+            dm = (time.perf_counter() - t0) * 1e3
+            ctx.start(b, steps + 2, seed=args.seed)
+            ctx.step_async(1, False)
+            ctx.fetch(1, 2)
+            t0 = time.perf_counter()
+            for i in range(2, steps + 2):
+                ctx.step_async(i, i % 2 == 0)
+            ctx.fetch(2, steps + 2)
+            dt = (time.perf_counter() - t0) * 1e3 / steps
+            if rep >= 0:
+                tm.append(dm)
+                ts.append(dt)
+        rbl.check_moments(mo)
+        out["call"] = {"matrix": "band", "n": nb, "nvec": b, "degree": d, "lo": lo, "hi": hi,
+                       "estimated": [lo0, hi0],
+                       "spmm_kernel": ctx.spmm_kernel_for(b), "moments_ms": _stats(tm),
+                       "term_ms": statistics.median(tm) / d, "step_ms": _stats(ts),
+                       "block_steps": statistics.median(tm) / statistics.median(ts)}
+        print(f"moments call: {out['call']}", flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--moments", action="store_true",
+                    help="time the Chebyshev moment pass and a moments call instead (see bench_moments)")
+    ap.add_argument("--n-moments", type=int, default=10_000_000)
+    ap.add_argument("--n-headline", type=int, default=10_000_000)
+    ap.add_argument("--moments-degree", type=int, default=100)
     ap.add_argument("--series", action="store_true",
                     help="time the Chebyshev series operator instead (see bench_series)")
     ap.add_argument("--n-series", type=int, default=1 << 21)
@@ -204,6 +274,16 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "filter_bench.json"))
     args = ap.parse_args()
     import rbl
+    if args.moments:
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(ROOT, "profiles", "moments_bench.json")
+        doc = {"tool": "tools/bench_filter.py --moments", "results": bench_moments(rbl, args)}
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(json.dumps({"wrote": args.out}))
+        return
     if args.series:
         if args.out == ap.get_default("out"):
             args.out = os.path.join(ROOT, "profiles", "series_bench.json")
