@@ -230,10 +230,21 @@ constexpr int64_t kRectPack = 512;     // nonzeros per packed short-row task (<=
 // same arrays whatever order the fill ran in.  nnz < 2^31.  Returns 0 or a hipError_t.
 int rect_transpose(int64_t rows, int64_t cols, int64_t nnz, const int64_t* ptr, const int32_t* ind,
                    const double* val, int64_t* tptr, int32_t* tind, double* tval, hipStream_t s);
-// out = T Q (- Qprev Bi^T if Qprev) (columns scaled by scale[c] if scale): Q, out, Qprev
-// row-major with b columns, any b >= 1; out has T's rows, Q the rows T's ids index.
+// out = T Q (- sa sw^T if sa) (- Qprev Bi^T if Qprev) (columns scaled by scale[c] if scale): Q,
+// out, Qprev row-major with b columns, any b >= 1; out has T's rows, Q the rows T's ids index.
+// sa / sw: the rank-one shift of rbl_set_rect_shift, out[row][c] -= sa[row] * sw[c] (sa: one
+// entry per row of T, sw: b entries, both on the device; both null: no shift, the arithmetic of
+// the unshifted pass).  Empty rows receive it, long rows once in the fix-up.
 void spmm_rect(const CsrDev::Tier& T, const double* Q, int b, double* out, const double* Qprev,
-               const double* Bi, const double* scale, hipStream_t s);
+               const double* Bi, const double* scale, hipStream_t s, const double* sa = nullptr,
+               const double* sw = nullptr);
+// w[c] = sum_r a[r] X[r][c], c < b: the weighted column sums of a row-major rows x b block
+// (t = Q^T v and s = Y^T u of the shifted operator), 1 <= b <= RBL_MAX_BLOCK.  part holds
+// rect_colsum_grid(rows, b) x b doubles (per-workgroup partials, added by reduce_slab); a fixed
+// summation order, no atomics; 16-byte loads when b is even and X is 16-byte aligned.
+int rect_colsum_grid(int64_t rows, int b);
+void rect_colsum(int64_t rows, int b, const double* a, const double* X, double* part, double* w,
+                 hipStream_t s);
 // spmm_panel.hip: column-panel CSR kernel for wide bands (b = 32, Q rows [q_lo, q_hi)); false
 // if not applicable.  panel_width(): Q rows per panel.
 bool spmm_panel(const CsrDev& A, const double* Qin, int64_t col_off, int b, double* U,

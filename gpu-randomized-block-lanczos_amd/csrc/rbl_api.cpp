@@ -133,6 +133,15 @@ struct rbl_ctx {
   SegTierBuf rect_side[2];
   double* d_rect_y = nullptr;  // m x rect_y_cols
   int rect_y_cols = 0;
+  // rank-one shift C = B - u v^T (rbl_set_rect_shift): the operator is then C^T C.  d_rect_ts
+  // holds t = Q^T v and s = Y^T u (rect_ts_cols doubles each), d_rect_part the workgroup
+  // partials of their reductions; both sized by ensure_rect_y
+  bool rect_shift = false;
+  double* d_shift_u = nullptr;  // m
+  double* d_shift_v = nullptr;  // n
+  double* d_rect_ts = nullptr;
+  double* d_rect_part = nullptr;
+  int rect_ts_cols = 0;
   int64_t ntiles = 0, tiles_per_wg = 0;
   bool window_ok16 = false, window_ok32 = false;
   bool band_ok16 = false, band_ok32 = false;
@@ -1508,15 +1517,28 @@ CsrDev::Tier rect_tier(const rbl_ctx* ctx, int side) {
   D.scratch = T.scratch;
   return D;
 }
-// the m x b work block Y = B Q_i of the normal operator
+// the m x b work block Y = B Q_i of the normal operator, and with a shift set the small buffers
+// of its two reductions (t, s: b doubles each; the workgroup partials of the larger side)
 int ensure_rect_y(rbl_ctx* ctx, int b) {
-  if (ctx->d_rect_y && ctx->rect_y_cols >= b) return RBL_OK;
-  HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(ctx->d_rect_y);
-  ctx->d_rect_y = nullptr;
-  ctx->rect_y_cols = 0;
-  HIPC(hipMalloc(&ctx->d_rect_y, (size_t)ctx->rect_m * b * sizeof(double)));
-  ctx->rect_y_cols = b;
+  if (!ctx->d_rect_y || ctx->rect_y_cols < b) {
+    HIPC(hipStreamSynchronize(ctx->stream));
+    hipFree(ctx->d_rect_y);
+    ctx->d_rect_y = nullptr;
+    ctx->rect_y_cols = 0;
+    HIPC(hipMalloc(&ctx->d_rect_y, (size_t)ctx->rect_m * b * sizeof(double)));
+    ctx->rect_y_cols = b;
+  }
+  if (ctx->rect_shift && ctx->rect_ts_cols < b) {
+    HIPC(hipStreamSynchronize(ctx->stream));
+    hipFree(ctx->d_rect_ts);
+    hipFree(ctx->d_rect_part);
+    ctx->d_rect_ts = ctx->d_rect_part = nullptr;
+    ctx->rect_ts_cols = 0;
+    const size_t grid = (size_t)rect_colsum_grid(std::max(ctx->rect_m, ctx->n), b);
+    HIPC(hipMalloc(&ctx->d_rect_ts, (size_t)2 * b * sizeof(double)));
+    HIPC(hipMalloc(&ctx->d_rect_part, grid * b * sizeof(double)));
+    ctx->rect_ts_cols = b;
+  }
   return RBL_OK;
 }
 
@@ -1570,8 +1592,21 @@ int apply_A(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* U, cons
   if (ctx->nloc <= 0) return 0;
   if (ctx->rect) {  // B^T (B Q_i): two gather passes, the 3-term epilogue fused into the second
     CHK(ensure_rect_y(ctx, b));
-    spmm_rect(rect_tier(ctx, 0), Qin + (0 - off) * b, b, ctx->d_rect_y, nullptr, nullptr, nullptr,
-              ctx->stream);
+    const double* Q = Qin + (0 - off) * b;
+    if (ctx->rect_shift) {
+      // C^T (C Q_i), C = B - u v^T:  t = Q^T v,  Y = B Q - u t^T,  s = Y^T u,
+      // U = B^T Y - v s^T (- Q_{i-1} B_i^T) — all in stream order, t and s never leave the device
+      double *t = ctx->d_rect_ts, *sv = ctx->d_rect_ts + b;
+      rect_colsum(ctx->n, b, ctx->d_shift_v, Q, ctx->d_rect_part, t, ctx->stream);
+      spmm_rect(rect_tier(ctx, 0), Q, b, ctx->d_rect_y, nullptr, nullptr, nullptr, ctx->stream,
+                ctx->d_shift_u, t);
+      rect_colsum(ctx->rect_m, b, ctx->d_shift_u, ctx->d_rect_y, ctx->d_rect_part, sv, ctx->stream);
+      spmm_rect(rect_tier(ctx, 1), ctx->d_rect_y, b, U, Qprev, Bi, nullptr, ctx->stream,
+                ctx->d_shift_v, sv);
+      ctx->path_stats[RBL_PATH_SPMM] += 1;
+      return 0;
+    }
+    spmm_rect(rect_tier(ctx, 0), Q, b, ctx->d_rect_y, nullptr, nullptr, nullptr, ctx->stream);
     spmm_rect(rect_tier(ctx, 1), ctx->d_rect_y, b, U, Qprev, Bi, nullptr, ctx->stream);
     ctx->path_stats[RBL_PATH_SPMM] += 1;
     return 0;
@@ -2319,6 +2354,16 @@ void free_run(rbl_ctx* ctx) {
   ctx->have_bprev = false;
 }
 
+// the rank-one shift of a rectangular B and the buffers of its reductions
+void free_rect_shift(rbl_ctx* ctx) {
+  hipFree(ctx->d_shift_u); ctx->d_shift_u = nullptr;
+  hipFree(ctx->d_shift_v); ctx->d_shift_v = nullptr;
+  hipFree(ctx->d_rect_ts); ctx->d_rect_ts = nullptr;
+  hipFree(ctx->d_rect_part); ctx->d_rect_part = nullptr;
+  ctx->rect_ts_cols = 0;
+  ctx->rect_shift = false;
+}
+
 void free_matrix(rbl_ctx* ctx) {
   hipFree(ctx->d_rowptr); ctx->d_rowptr = nullptr;
   hipFree(ctx->d_col); ctx->d_col = nullptr;
@@ -2345,6 +2390,7 @@ void free_matrix(rbl_ctx* ctx) {
   free_tiers(ctx);
   for (auto& T : ctx->rect_side) free_seg(T, true);
   hipFree(ctx->d_rect_y); ctx->d_rect_y = nullptr; ctx->rect_y_cols = 0;
+  free_rect_shift(ctx);
   ctx->rect = false;
   ctx->rect_m = 0;
   hipFree(ctx->d_dense); ctx->d_dense = nullptr;
@@ -3087,10 +3133,20 @@ int rbl_get_matrix_rect(rbl_ctx* ctx, int trans, int64_t* rowptr, int32_t* colin
 }
 
 namespace {
-// Y (rows of side `trans`) = side X (* scale per column), host column-major blocks of w columns
-static int rect_apply_host(rbl_ctx* ctx, int trans, int w, const double* X, double* Y, const double* scale) {
+// Y (rows of side `trans`) = side X (* scale per column), host column-major blocks of w columns.
+// shifted (and a shift set): side is C = B - u v^T or C^T, i.e. Y = B X - u (v^T X) or
+// Y = B^T X - v (u^T X), the b-vector reduced on the device, the shift before the scale.
+static int rect_apply_host(rbl_ctx* ctx, int trans, int w, const double* X, double* Y, const double* scale,
+                           bool shifted = false) {
   const int64_t rin = trans ? ctx->rect_m : ctx->n, rout = trans ? ctx->n : ctx->rect_m;
-  DevBuf x, xr, y, sc;
+  shifted = shifted && ctx->rect_shift;
+  const double* sa = !shifted ? nullptr : trans ? ctx->d_shift_v : ctx->d_shift_u;    // per output row
+  const double* sin = !shifted ? nullptr : trans ? ctx->d_shift_u : ctx->d_shift_v;   // per input row
+  DevBuf x, xr, y, sc, sw, part;
+  if (shifted) {
+    HIPC(hipMalloc(&sw.p, w * sizeof(double)));
+    HIPC(hipMalloc(&part.p, (size_t)rect_colsum_grid(rin, w) * w * sizeof(double)));
+  }
   const int64_t rmax = std::max(rin, rout);
   HIPC(hipMalloc(&x.p, rmax * w * sizeof(double)));
   HIPC(hipMalloc(&xr.p, rin * w * sizeof(double)));
@@ -3103,7 +3159,9 @@ static int rect_apply_host(rbl_ctx* ctx, int trans, int w, const double* X, doub
   colmajor_to_rowmajor(x.d(), rin, w, xr.d(), ctx->stream);
   {
     StageScope t(ctx, RBL_STAGE_AQ);
-    spmm_rect(rect_tier(ctx, trans), xr.d(), w, y.d(), nullptr, nullptr, sc.d(), ctx->stream);
+    if (shifted) rect_colsum(rin, w, sin, xr.d(), part.d(), sw.d(), ctx->stream);
+    spmm_rect(rect_tier(ctx, trans), xr.d(), w, y.d(), nullptr, nullptr, sc.d(), ctx->stream, sa,
+              sw.d());
   }
   HIPC(hipGetLastError());
   rowmajor_to_colmajor(y.d(), rout, w, x.d(), ctx->stream);
@@ -3129,7 +3187,49 @@ int rbl_left_vectors(rbl_ctx* ctx, int k, const double* V, const double* sigma, 
   HIPC(hipSetDevice(ctx->device));
   std::vector<double> inv(k);
   for (int j = 0; j < k; ++j) inv[j] = 1.0 / sigma[j];  // U = (B V) ./ transpose(D), images.jl:24
-  return rect_apply_host(ctx, 0, k, V, U_out, inv.data());
+  return rect_apply_host(ctx, 0, k, V, U_out, inv.data(), true);  // with a shift: (C V) ./ ...
+}
+
+int rbl_set_rect_shift(rbl_ctx* ctx, const double* u, const double* v) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (!ctx->rect) return fail(ctx, RBL_ERR_STATE, "rbl_set_rect_shift: no rectangular matrix");
+  if ((u == nullptr) != (v == nullptr))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_rect_shift: u and v must both be given or both be NULL");
+  HIPC(hipSetDevice(ctx->device));
+  if (!u) {  // clear: the operator is B^T B again
+    HIPC(hipStreamSynchronize(ctx->stream));
+    free_rect_shift(ctx);
+    return RBL_OK;
+  }
+  const int64_t m = ctx->rect_m, n = ctx->n;
+  for (int64_t i = 0; i < m; ++i)
+    if (!std::isfinite(u[i])) return fail(ctx, RBL_ERR_INVALID, "rbl_set_rect_shift: u has a non-finite entry");
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return fail(ctx, RBL_ERR_INVALID, "rbl_set_rect_shift: v has a non-finite entry");
+  HIPC(hipStreamSynchronize(ctx->stream));  // steps in flight still read the old vectors
+  if (!ctx->d_shift_u) HIPC(hipMalloc(&ctx->d_shift_u, m * sizeof(double)));
+  if (!ctx->d_shift_v) HIPC(hipMalloc(&ctx->d_shift_v, n * sizeof(double)));
+  HIPC(hipMemcpy(ctx->d_shift_u, u, m * sizeof(double), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->d_shift_v, v, n * sizeof(double), hipMemcpyHostToDevice));
+  ctx->rect_shift = true;
+  return RBL_OK;
+}
+
+int rbl_get_rect_shift(rbl_ctx* ctx, double* u_out, double* v_out) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (!ctx->rect || !ctx->rect_shift) return fail(ctx, RBL_ERR_STATE, "rbl_get_rect_shift: no shift set");
+  HIPC(hipSetDevice(ctx->device));
+  if (u_out) HIPC(hipMemcpy(u_out, ctx->d_shift_u, ctx->rect_m * sizeof(double), hipMemcpyDeviceToHost));
+  if (v_out) HIPC(hipMemcpy(v_out, ctx->d_shift_v, ctx->n * sizeof(double), hipMemcpyDeviceToHost));
+  return RBL_OK;
+}
+
+int rbl_apply_rect_shifted(rbl_ctx* ctx, int trans, int b, const double* X, double* Y) {
+  if (!ctx || (trans != 0 && trans != 1) || b < 1 || b > RBL_MAX_BLOCK || !X || !Y)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_apply_rect_shifted: bad arguments");
+  if (!ctx->rect) return fail(ctx, RBL_ERR_STATE, "rbl_apply_rect_shifted: no rectangular matrix");
+  HIPC(hipSetDevice(ctx->device));
+  return rect_apply_host(ctx, trans, b, X, Y, nullptr, true);
 }
 
 int rbl_matrix_info(rbl_ctx* ctx, int64_t* n, int64_t* row_begin, int64_t* row_end,

@@ -14,11 +14,18 @@
 // chunks.  Output rows differ from input rows, there is no band or tile metadata, and empty
 // rows (packed like any short row) are written as zeros (+ the epilogue).
 //
+// A rank-one shift C = B - u v^T (rbl_set_rect_shift: centring, correspondence analysis,
+// deflating a known pair) rides in the epilogue of both passes as out[row, c] -= a[row] w[c]
+// with w = X^T (the other shift vector), b values formed on the device by rect_colsum in a
+// fixed order, so C^T C is applied with nothing dense formed and no host round trip.
+//
 // Algorithmic bytes per pass: nnz * 12 + (rows + 1) * 8 + rows * b * 8 (+ n * b * 8 for
 // Q_{i-1} in pass 2); the gathered Q rows, nnz * b * 8, are cache traffic.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <atomic>
+#include <cstdint>
 
 #include "kernels.hpp"
 
@@ -129,15 +136,20 @@ int rect_transpose(int64_t rows, int64_t cols, int64_t nnz, const int64_t* ptr, 
 // ----------------------------------------------------------------------------------------
 // out[row, c] = (sum_k val[k] Q[ind[k], c]  - sum_u Qprev[row, u] Bi[c, u]) * scale[c]
 // for the columns c in [c0, c0 + BP) of b; Q, out, Qprev row-major with leading dimension b.
+// SHIFT (sa, sw non-null): the row's sum is followed by  - sa[row] sw[c]  before the Qprev term
+// and the scale; empty rows take it like any other, long rows in k_rect_fixup.  Without SHIFT
+// the two pointers are unused and the kernel is the unshifted one, instruction for instruction;
+// with it the kernel keeps the unshifted one's waves per SIMD (8; 7 at BP = 8).
 // ----------------------------------------------------------------------------------------
-template <int BP>
+template <int BP, bool SHIFT>
 __global__ __launch_bounds__(256) void k_rect_spmm(
     int64_t ntasks, const int64_t* __restrict__ trow, const int32_t* __restrict__ tinfo,
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ ind,
     const double* __restrict__ val, const double* __restrict__ Q, int b, int c0,
     double* __restrict__ U, double* __restrict__ scratch, const int64_t* __restrict__ slot_k0,
     const double* __restrict__ Qprev, const double* __restrict__ Bi,
-    const double* __restrict__ scale) {
+    const double* __restrict__ scale, const double* __restrict__ sa,
+    const double* __restrict__ sw) {
   constexpr int R = kWave / BP;
   constexpr int G = BP < 8 ? BP : 8;  // Q-row gathers issued back to back per lane group
   // B_i for the epilogue in LDS when it is at most 32 x 32 (bs[u * BP + c] = B_i[c][u]: a lane
@@ -189,6 +201,13 @@ __global__ __launch_bounds__(256) void k_rect_spmm(
     for (int rr = h; rr < info; rr += R) {  // lane-group-uniform row loop
       const int64_t row = r0 + rr;
       double acc = dot(rowptr[row], rowptr[row + 1], BP);
+      if constexpr (SHIFT) {
+        // sw[c] is read here, after the row's sum, through an index the compiler cannot hoist:
+        // held across the row loop it would cost the two registers that decide the occupancy
+        int wi = cs;
+        asm volatile("" : "+v"(wi));
+        acc = fma(-sa[row], sw[wi], acc);
+      }
       if (Qprev) {
         if constexpr (kBlds) {
           const double qv = Qprev[row * b + cs];
@@ -220,7 +239,9 @@ __global__ __launch_bounds__(256) void k_rect_fixup(int64_t nlong, const int64_t
                                                    double* __restrict__ U,
                                                    const double* __restrict__ Qprev,
                                                    const double* __restrict__ Bi,
-                                                   const double* __restrict__ scale) {
+                                                   const double* __restrict__ scale,
+                                                   const double* __restrict__ sa,
+                                                   const double* __restrict__ sw) {
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t i = g / BP;
   if (i >= nlong) return;
@@ -229,6 +250,7 @@ __global__ __launch_bounds__(256) void k_rect_fixup(int64_t nlong, const int64_t
   const int64_t row = lrow[i];
   double acc = 0.0;
   for (int64_t sl = lslot[i]; sl < lslot[i + 1]; ++sl) acc += scratch[sl * kWave + j];
+  if (sa) acc = fma(-sa[row], sw[c], acc);
   if (Qprev)
     for (int u = 0; u < b; ++u) acc = fma(-Qprev[row * b + u], Bi[(int64_t)c * b + u], acc);
   U[row * b + c] = scale ? acc * scale[c] : acc;
@@ -236,31 +258,123 @@ __global__ __launch_bounds__(256) void k_rect_fixup(int64_t nlong, const int64_t
 
 template <int BP>
 static void launch_rect(const CsrDev::Tier& T, const double* Q, int b, int c0, double* out,
-                        const double* Qprev, const double* Bi, const double* scale, hipStream_t s) {
+                        const double* Qprev, const double* Bi, const double* scale,
+                        const double* sa, const double* sw, hipStream_t s) {
   const int64_t blocks = (T.ntasks + 3) / 4;
-  hipLaunchKernelGGL((k_rect_spmm<BP>), dim3((unsigned)blocks), dim3(256), 0, s, T.ntasks, T.trow,
-                     T.tinfo, T.rowptr, T.col, T.val, Q, b, c0, out, T.scratch, T.slot_k0, Qprev, Bi,
-                     scale);
+  if (sa)
+    hipLaunchKernelGGL((k_rect_spmm<BP, true>), dim3((unsigned)blocks), dim3(256), 0, s, T.ntasks,
+                       T.trow, T.tinfo, T.rowptr, T.col, T.val, Q, b, c0, out, T.scratch, T.slot_k0,
+                       Qprev, Bi, scale, sa, sw);
+  else
+    hipLaunchKernelGGL((k_rect_spmm<BP, false>), dim3((unsigned)blocks), dim3(256), 0, s, T.ntasks,
+                       T.trow, T.tinfo, T.rowptr, T.col, T.val, Q, b, c0, out, T.scratch, T.slot_k0,
+                       Qprev, Bi, scale, sa, sw);
   if (T.nlong > 0) {
     const int64_t th = T.nlong * BP;
     hipLaunchKernelGGL((k_rect_fixup<BP>), dim3((unsigned)((th + 255) / 256)), dim3(256), 0, s,
-                       T.nlong, T.lrow, T.lslot, T.scratch, b, c0, out, Qprev, Bi, scale);
+                       T.nlong, T.lrow, T.lslot, T.scratch, b, c0, out, Qprev, Bi, scale, sa,
+                       sw);
   }
 }
 
 void spmm_rect(const CsrDev::Tier& T, const double* Q, int b, double* out, const double* Qprev,
-               const double* Bi, const double* scale, hipStream_t s) {
+               const double* Bi, const double* scale, hipStream_t s, const double* sa,
+               const double* sw) {
   if (T.ntasks <= 0 || b < 1) return;
+  if (!sa || !sw) sa = sw = nullptr;
   if (b > 32) {  // 64-lane groups; b > 64 in 64-column chunks (the scratch is reused in stream order)
-    for (int c0 = 0; c0 < b; c0 += 64) launch_rect<64>(T, Q, b, c0, out, Qprev, Bi, scale, s);
+    for (int c0 = 0; c0 < b; c0 += 64) launch_rect<64>(T, Q, b, c0, out, Qprev, Bi, scale, sa, sw, s);
     return;
   }
-  if (b > 16) launch_rect<32>(T, Q, b, 0, out, Qprev, Bi, scale, s);
-  else if (b > 8) launch_rect<16>(T, Q, b, 0, out, Qprev, Bi, scale, s);
-  else if (b > 4) launch_rect<8>(T, Q, b, 0, out, Qprev, Bi, scale, s);
-  else if (b > 2) launch_rect<4>(T, Q, b, 0, out, Qprev, Bi, scale, s);
-  else if (b > 1) launch_rect<2>(T, Q, b, 0, out, Qprev, Bi, scale, s);
-  else launch_rect<1>(T, Q, b, 0, out, Qprev, Bi, scale, s);
+  if (b > 16) launch_rect<32>(T, Q, b, 0, out, Qprev, Bi, scale, sa, sw, s);
+  else if (b > 8) launch_rect<16>(T, Q, b, 0, out, Qprev, Bi, scale, sa, sw, s);
+  else if (b > 4) launch_rect<8>(T, Q, b, 0, out, Qprev, Bi, scale, sa, sw, s);
+  else if (b > 2) launch_rect<4>(T, Q, b, 0, out, Qprev, Bi, scale, sa, sw, s);
+  else if (b > 1) launch_rect<2>(T, Q, b, 0, out, Qprev, Bi, scale, sa, sw, s);
+  else launch_rect<1>(T, Q, b, 0, out, Qprev, Bi, scale, sa, sw, s);
+}
+
+// ----------------------------------------------------------------------------------------
+// part[g][c] = workgroup g's share of  w[c] = sum_r a[r] X[r, c]  (X row-major rows x b): the
+// b-vectors t = Q^T v and s = Y^T u of the shifted operator.  Built as k_cheb_moment
+// (spmm_cheb.hip): a row is cw slots of type T (d2v: b / 2 column pairs, 16-byte loads; double:
+// b columns), a thread keeps its slot for the whole pass, the workgroup covers a tile of
+// nrg = 256 / cw rows at a time (one contiguous stream) and walks the tiles grid-stride; a row
+// wider than 256 slots runs in chunks of 256.  Fixed order: each thread over its rows
+// ascending, the row groups ascending in LDS, the workgroups by reduce_slab.  No atomics.
+// ----------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kColsumThreads = 256;
+constexpr int kColsumPerCu = 8;  // workgroups per CU (2 waves per SIMD x 4), as the stream passes
+
+int rect_cu_count() {
+  static std::atomic<int> cus[64];  // per device; zero-initialised (static storage)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  int v = cus[dev].load(std::memory_order_relaxed);
+  if (v == 0) {
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
+      v = 256;
+    cus[dev].store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kColsumThreads) void k_rect_colsum(int64_t rows, int cw,
+                                                                const double* __restrict__ a,
+                                                                const T* __restrict__ X,
+                                                                double* __restrict__ part) {
+  constexpr int VW = sizeof(T) / sizeof(double);  // columns per slot
+  __shared__ double sm[VW * kColsumThreads];
+  const int cwl = cw < kColsumThreads ? cw : kColsumThreads;  // slots of a row covered at once
+  const int nrg = kColsumThreads / cwl;                       // rows per tile
+  const int rg = threadIdx.x / cwl, cl = threadIdx.x % cwl;
+  const int64_t rstride = (int64_t)gridDim.x * nrg;
+  double* out = part + (int64_t)blockIdx.x * VW * cw;
+  for (int cb = 0; cb < cw; cb += cwl) {
+    const int c = cb + cl;
+    T acc = T(0.0);
+    if (rg < nrg && c < cw)
+      for (int64_t r = (int64_t)blockIdx.x * nrg + rg; r < rows; r += rstride) acc += a[r] * X[r * cw + c];
+    if constexpr (VW == 2) {
+      sm[threadIdx.x] = acc.x;
+      sm[kColsumThreads + threadIdx.x] = acc.y;
+    } else {
+      sm[threadIdx.x] = acc;
+    }
+    __syncthreads();
+    const int ncl = cw - cb < cwl ? cw - cb : cwl;  // slots of this chunk
+    for (int idx = threadIdx.x; idx < VW * ncl; idx += kColsumThreads) {
+      const int v = idx / ncl, c2 = idx % ncl;
+      double sum = 0.0;
+      for (int g = 0; g < nrg; ++g) sum += sm[v * kColsumThreads + g * cwl + c2];
+      out[(cb + c2) * VW + v] = sum;
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+int rect_colsum_grid(int64_t rows, int b) {
+  const int64_t want = (rows * ((b + 1) / 2) + kColsumThreads - 1) / kColsumThreads;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)rect_cu_count() * kColsumPerCu));
+}
+
+void rect_colsum(int64_t rows, int b, const double* a, const double* X, double* part, double* w,
+                 hipStream_t s) {
+  if (rows <= 0 || b < 1) return;
+  const int grid = rect_colsum_grid(rows, b);
+  // a thread keeps a column pair only when every row starts on a pair: b even, X 16-byte aligned
+  if (b % 2 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0)
+    hipLaunchKernelGGL((k_rect_colsum<d2v>), dim3(grid), dim3(kColsumThreads), 0, s, rows, b / 2, a,
+                       reinterpret_cast<const d2v*>(X), part);
+  else
+    hipLaunchKernelGGL((k_rect_colsum<double>), dim3(grid), dim3(kColsumThreads), 0, s, rows, b, a, X,
+                       part);
+  reduce_slab(part, grid, b, w, nullptr, s);
 }
 
 }  // namespace rbl

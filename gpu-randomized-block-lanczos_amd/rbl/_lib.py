@@ -82,6 +82,9 @@ SIGNATURES = {
     "rbl_get_matrix_rect": (C.c_int, [_p, C.c_int, _pi64, _pi32, _pd]),
     "rbl_apply_rect": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd]),
     "rbl_left_vectors": (C.c_int, [_p, C.c_int, _pd, _pd, _pd]),
+    "rbl_set_rect_shift": (C.c_int, [_p, _pd, _pd]),
+    "rbl_get_rect_shift": (C.c_int, [_p, _pd, _pd]),
+    "rbl_apply_rect_shifted": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd]),
     "rbl_gen_matrix_hashwindow": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_circuit": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_rmat": (C.c_int, [_p, _i64, C.c_int, _i64, C.c_double, C.c_double, C.c_double,

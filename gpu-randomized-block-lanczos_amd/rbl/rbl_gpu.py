@@ -204,8 +204,43 @@ class Context:
                     "rbl_apply_rect")
         return Y
 
+    def set_rect_shift(self, u, v) -> None:
+        """Rank-one shift C = B - u v^T of the rectangular B held (rbl_set_rect_shift): u of
+        length m, v of length n, both copied to the device; ``None, None`` clears it.  While set,
+        apply / start / step / ritz_project run on C^T C and left_vectors returns C V / sigma."""
+        if u is None and v is None:
+            self._check(lib.rbl_set_rect_shift(self._h, None, None), "rbl_set_rect_shift")
+            return
+        m, n, _ = self.rect_info()
+        u = None if u is None else np.ascontiguousarray(u, dtype=np.float64).ravel()
+        v = None if v is None else np.ascontiguousarray(v, dtype=np.float64).ravel()
+        if (u is not None and u.size != m) or (v is not None and v.size != n):
+            raise ValueError(f"set_rect_shift: u must have {m} entries and v {n}")
+        self._check(lib.rbl_set_rect_shift(self._h, dptr(u), dptr(v)), "rbl_set_rect_shift")
+
+    def get_rect_shift(self):
+        """(u, v) of the shift set (rbl_get_rect_shift); RBLError (RBL_ERR_STATE) when none is."""
+        m, n, _ = self.rect_info()
+        u, v = np.zeros(m), np.zeros(n)
+        self._check(lib.rbl_get_rect_shift(self._h, dptr(u), dptr(v)), "rbl_get_rect_shift")
+        return u, v
+
+    def apply_rect_shifted(self, X: np.ndarray, trans: bool = False) -> np.ndarray:
+        """Y = C X (X: n x b), or with trans Y = C^T X (X: m x b), C = B - u v^T: one pass of the
+        shifted pair.  Without a shift the bits of apply_rect."""
+        m, n, _ = self.rect_info()
+        rin, rout = (m, n) if trans else (n, m)
+        X = np.asfortranarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] != rin:
+            raise ValueError(f"apply_rect_shifted: X must have {rin} rows")
+        Y = np.zeros((rout, X.shape[1]), order="F")
+        self._check(lib.rbl_apply_rect_shifted(self._h, int(bool(trans)), X.shape[1], dptr(X),
+                                               dptr(Y)), "rbl_apply_rect_shifted")
+        return Y
+
     def left_vectors(self, V: np.ndarray, sigma) -> np.ndarray:
-        """U = B V diag(1 / sigma) (images.jl:24), m x k, from V (n x k) and the singular values."""
+        """U = B V diag(1 / sigma) (images.jl:24), m x k, from V (n x k) and the singular values
+        (with a shift set: C V diag(1 / sigma))."""
         m, n, _ = self.rect_info()
         V = np.asfortranarray(V, dtype=np.float64)
         sigma = np.ascontiguousarray(sigma, dtype=np.float64).ravel()

@@ -30,21 +30,44 @@ def _validate(B, k, side):
     return m, n
 
 
+def _validate_shift(shift, m, n):
+    """(u, v) as float64 vectors of lengths m and n, finite; ValueError otherwise."""
+    try:
+        u, v = shift
+    except (TypeError, ValueError):
+        raise ValueError("RBL_svd: shift must be a pair (u, v)") from None
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if u.shape != (m,) or v.shape != (n,):
+        raise ValueError(f"RBL_svd: shift = (u, v) needs u of length m = {m} and v of length n = {n}")
+    if not (np.all(np.isfinite(u)) and np.all(np.isfinite(v))):
+        raise ValueError("RBL_svd: shift has a non-finite entry")
+    return u, v
+
+
 def RBL_svd(B, k: int, b: int, *, side: str = "auto", omega=None, seed: int = 0,
-            kryl_sz: int = KRYL_SZ_GPU, return_info: bool = False, device: int = 0):
+            kryl_sz: int = KRYL_SZ_GPU, return_info: bool = False, device: int = 0, shift=None):
     """The k largest singular triplets of B (m x n): returns (U, S, V) with S descending,
     U m x k, V n x k, B V = U diag(S).
 
     side: the dimension the Krylov basis lives on — "right" iterates on B^T B (n rows: V are the
     Ritz vectors, U = B V / S), "left" on B B^T (m rows, by setting B^T — free through the layout
     flag — and swapping U and V at the end), "auto" the smaller of the two.  omega: the start
-    block (rows of the iterated dimension) instead of the seeded device draw."""
+    block (rows of the iterated dimension) instead of the seeded device draw.
+
+    shift: a pair (u, v), u of length m and v of length n, for the triplets of the rank-one
+    shifted C = B - u v^T instead (rbl_set_rect_shift; C is never formed): C V = U diag(S).
+    ``(ones(m), column means)`` is PCA's centring (``RBL_pca``)."""
     m, n = _validate(B, k, side)
     if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b < 1:
         raise ValueError("RBL_svd: b must be an integer >= 1")
+    if shift is not None:
+        shift = _validate_shift(shift, m, n)
     left = side == "left" or (side == "auto" and m < n)
     with Context(device) as ctx:
         ctx.set_matrix_normal(B.T if left else B)   # CSR <-> CSC views: no host conversion
+        if shift is not None:                       # C^T = B^T - v u^T: the pair swaps with the side
+            ctx.set_rect_shift(*(shift[::-1] if left else shift))
         D, V, info = lanczos(ctx, k, b, kryl_sz=kryl_sz, omega=omega, seed=seed)
         S = np.sqrt(np.maximum(D, 0.0))
         U = ctx.left_vectors(V, S)

@@ -250,8 +250,38 @@ int rbl_get_matrix_rect(rbl_ctx* ctx, int trans, int64_t* rowptr, int32_t* colin
 int rbl_apply_rect(rbl_ctx* ctx, int trans, int b, const double* X, double* Y);
 /* Left singular vectors U_out (nrows x k, column-major) = B V diag(1 / sigma) — images.jl:24,
  * `U = (B*V) ./ transpose(D)` — from V (ncols x k, column-major) and the k singular values:
- * pass 1 of the pair with the per-column scale in its epilogue.  k <= RBL_MAX_BLOCK. */
+ * pass 1 of the pair with the per-column scale in its epilogue.  k <= RBL_MAX_BLOCK.  With a
+ * shift set (rbl_set_rect_shift) U_out = (B V - u (v^T V)) diag(1 / sigma) = C V diag(1 / sigma),
+ * the shift subtracted before the scale. */
 int rbl_left_vectors(rbl_ctx* ctx, int k, const double* V, const double* sigma, double* U_out);
+/* Rank-one shift of the rectangular B held: C = B - u v^T (u: nrows entries, v: ncols entries,
+ * both copied to the device; the caller's arrays are not kept).  PCA with implicit centring is
+ * u = 1, v = the column means; centring on the other side, correspondence analysis
+ * (B - r c^T / N) and the removal of a known singular pair are other choices of u, v.  C is
+ * never formed: a block step applies
+ *     t = Q^T v,   Y = B Q - u t^T,   s = Y^T u,   U = B^T Y - v s^T (- Q_{i-1} B_i^T)
+ * — the two gather passes with  out[row][c] -= a[row] * w[c]  in their epilogues and two
+ * reductions to b values each, all enqueued on the context's stream with no host
+ * synchronisation; every sum has a fixed order (no atomics), so two runs give the same bits.
+ * The operator is exactly C^T C for whatever u, v are stored (symmetric for any shift).
+ * While a shift is set rbl_apply, rbl_start, rbl_step, rbl_step_async, the restarted entry
+ * points and rbl_ritz_project run on C^T C and rbl_left_vectors returns C V diag(1 / sigma);
+ * rbl_apply_rect stays the plain B / B^T.  Set it before rbl_start: a run in flight is waited
+ * for, and its basis belongs to the operator it was built with.
+ * Both NULL clears the shift (results are then bit for bit those of a context that never had
+ * one); setting any matrix clears it too.  RBL_ERR_STATE without a rectangular matrix;
+ * RBL_ERR_INVALID when exactly one pointer is NULL or an entry is not finite — the context and
+ * an earlier shift stay as they were.  Limits as for the rectangular path: one rank, fp64 basis,
+ * no filter.  Extra device memory: (nrows + ncols) x 8 B and under 8 workgroups per CU x b x 8 B. */
+int rbl_set_rect_shift(rbl_ctx* ctx, const double* u, const double* v);
+/* Download the shift set (u_out: nrows, v_out: ncols; either may be NULL) — test/inspection only.
+ * RBL_ERR_STATE when no shift is set. */
+int rbl_get_rect_shift(rbl_ctx* ctx, double* u_out, double* v_out);
+/* One pass of the shifted pair, host column-major blocks as for rbl_apply_rect: trans 0:
+ * Y (nrows x b) = C X = B X - u (v^T X);  trans 1: Y (ncols x b) = C^T X = B^T X - v (u^T X).
+ * Without a shift it equals rbl_apply_rect bit for bit.  b <= RBL_MAX_BLOCK; timed under "AQ"
+ * (the reduction included) while RBL_OPT_TIMERS is set. */
+int rbl_apply_rect_shifted(rbl_ctx* ctx, int trans, int b, const double* X, double* Y);
 int rbl_gen_matrix_hashwindow(rbl_ctx* ctx, int64_t n, int64_t halfwidth, double density,
                               uint64_t seed, int nplant, const double* plant);
 /* Device-side generator of the seeded symmetric R-MAT matrix (BASELINE

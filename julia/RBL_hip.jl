@@ -15,6 +15,7 @@
 #   D, V = RBL_hip(A, k, b; device_blocks = -1)   # hybrid buffer: what fits in HBM, rest on host
 #   D, V = RBL_hip_restarted(A, k)       # restarted.jl:106 (RBL_gpu_restarted)
 #   U, D, V = RBL_gpu_svd(B, k, b)       # images.jl:29-33 on a sparse rectangular B, B^T B implicit
+#   U, D, V, mu = RBL_gpu_pca(B, k, b)  # PCA of a sparse B: the triplets of B - 1 mu^T, never formed
 #   D, V, r = RBL_gpu_filtered(A, k, b; which = :SA, degree = 8)   # the k smallest (or :LA largest)
 #                                        # pairs through a Chebyshev filter, r = ||A v - D v||
 #   c, (lo, hi) = RBL_gpu_eigcount(A, x0, x1)     # expected number of eigenvalues in [x0, x1] (KPM)
@@ -76,6 +77,14 @@ function set_matrix_normal!(ctx, B::SparseMatrixCSC{Float64})
                          Cint(1)), "rbl_set_matrix_normal")
 end
 
+# The rank-one shift C = B - u v^T of the rectangular B held (rbl_set_rect_shift): u of length
+# size(B, 1), v of length size(B, 2), both copied to the device.  The operator is then C^T C and
+# rbl_left_vectors returns C V ./ transpose(D).
+function set_rect_shift!(ctx, u::Vector{Float64}, v::Vector{Float64})
+    rbl_check(ctx, ccall((:rbl_set_rect_shift, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx, u, v), "rbl_set_rect_shift")
+end
+
 function rbl_context(device::Int)
     hr = Ref{Ptr{Cvoid}}(C_NULL)
     st = ccall((:rbl_create, librbl_hip), Cint, (Ref{Ptr{Cvoid}}, Cint), hr, Cint(device))
@@ -111,13 +120,20 @@ end
 function RBL_hip(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k::Int64, b::Int64;
                  device::Int = 0, seed::UInt64 = rand(UInt64), kryl_sz::Int64 = 1200,
                  basis_bits::Int = (FLOAT == Float32 ? 32 : 64), device_blocks::Int = 0,
-                 timer = nothing, normal::Bool = false)
+                 timer = nothing, normal::Bool = false, shift = nothing)
     # normal: A is a rectangular B and the operator B^T B (RBL_gpu_svd); then the left singular
     # vectors are formed before the context is released and returned as a third value
+    # shift = (u, v) (normal only): the operator is C^T C, C = B - u v^T (RBL_gpu_pca)
+    shift === nothing || normal || throw(ArgumentError("RBL_hip: shift needs normal = true"))
+    if shift !== nothing
+        length(shift[1]) == size(A, 1) && length(shift[2]) == size(A, 2) ||
+            throw(ArgumentError("RBL_hip: shift = (u, v) needs length(u) = size(A, 1), length(v) = size(A, 2)"))
+    end
     n = size(A, 2)
     ctx = rbl_context(device)
     try
         normal ? set_matrix_normal!(ctx, A) : set_matrix!(ctx, A)
+        shift === nothing || set_rect_shift!(ctx, Vector{Float64}(shift[1]), Vector{Float64}(shift[2]))
         # RBL_OPT_DEVICE_BLOCKS: the hybrid GPU/host Krylov buffer (RBL_gpu.jl:24-27, 59-81)
         rbl_check(ctx, ccall((:rbl_set_option, librbl_hip), Cint, (Ptr{Cvoid}, Cint, Int64),
                              ctx, RBL_OPT_DEVICE_BLOCKS, device_blocks), "rbl_set_option")
@@ -251,6 +267,23 @@ function RBL_gpu_svd(B::SparseMatrixCSC{DOUBLE}, k::Int64, b::Int64)
     timer = isdefined(Main, :to) ? Main.to : nothing
     D, V, U = RBL_hip(B, k, b; timer = timer, normal = true, basis_bits = 64)
     return U, D, V
+end
+
+# PCA of a sparse data matrix B (m samples x n features) with implicit centring: the k largest
+# singular triplets of C = B - 1 mu^T, mu the column means (one pass over the nonzeros on the
+# host), through the rank-one shift (ones(m), mu) — C, which is dense, is never formed.  Returns
+# U (m x k, the scores are U .* transpose(D)), the singular values D of C (descending; the
+# explained variances are D.^2 ./ (m - 1)), V (n x k, the principal axes) and mu.
+function RBL_gpu_pca(B::SparseMatrixCSC{DOUBLE}, k::Int64, b::Int64)
+    timer = isdefined(Main, :to) ? Main.to : nothing
+    m, n = size(B)
+    mu = zeros(Float64, n)
+    for j in 1:n
+        mu[j] = sum(@view B.nzval[B.colptr[j]:B.colptr[j+1]-1]) / m
+    end
+    D, V, U = RBL_hip(B, k, b; timer = timer, normal = true, basis_bits = 64,
+                      shift = (ones(Float64, m), mu))
+    return U, D, V, mu
 end
 
 # restarted.jl:106-146 (RBL_gpu_restarted): b = 1 cycles with locking.  The cycle

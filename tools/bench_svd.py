@@ -18,6 +18,16 @@ Measured, with b = 32 and k = 20 by default:
     The two routes alternate in one process, each matrix uploaded once; per route the median
     wall time to its k triplets (Ritz vectors and, for the SVD route, the left vectors included),
     the spread (max - min), the steps, and the "AQ" stage ms per operator application.
+
+--shift: instead of the parts above, the shifted application next to the plain one — the
+pair C X, C^T Y of rbl_set_rect_shift (u = 1, v = the column means: PCA's centring) against
+B X, B^T Y, both through rbl_apply_rect_shifted on the same context and the same blocks, the arms
+alternating in one process (shift set, both passes, shift cleared, both passes, ...).  The "AQ"
+timer (hipEvents) covers each pass and, shifted, the reduction in front of it — the work a block
+step adds: one reduction over the n x b block and one over the m x b block.  Reported per arm:
+the median ms of the pair and the spread over --shift-rounds rounds of --pass-steps applications,
+the overhead (median of the per-round differences) and the byte estimate it is judged against:
+one read of Q and v ((n b + n) 8 B) and one of Y and u ((m b + m) 8 B).
 """
 from __future__ import annotations
 
@@ -56,6 +66,45 @@ def gen_B(m: int, n: int, k: int, seed: int):
     return indptr, indices, data, s
 
 
+def bench_shift(svd, indptr, indices, data, m, n, b, args):
+    """The shifted operator C^T C next to the plain B^T B on one context, arms alternating."""
+    mu = np.bincount(indices, weights=data, minlength=n) / m
+    ones = np.ones(m)
+    rng = np.random.default_rng(2)
+    Xn = np.asfortranarray(rng.standard_normal((n, b)))
+    Xm = np.asfortranarray(rng.standard_normal((m, b)))
+    from rbl import _lib
+    svd.set_option(_lib.RBL_OPT_TIMERS, 1)
+
+    def arm(shifted):
+        svd.set_rect_shift(*((ones, mu) if shifted else (None, None)))
+        total = 0.0
+        for X, trans in ((Xn, False), (Xm, True)):
+            svd.apply_rect_shifted(X, trans)                        # warm-up
+            svd.reset_timers()
+            for _ in range(args.pass_steps):
+                svd.apply_rect_shifted(X, trans)
+            total += svd.timers()["AQ"] / args.pass_steps
+        return total
+
+    plain, shifted = [], []
+    for _ in range(args.shift_rounds):
+        shifted.append(arm(True))
+        plain.append(arm(False))
+    plain, shifted = np.array(plain), np.array(shifted)
+    extra = (n * b + n + m * b + m) * 8
+    return {"rounds": args.shift_rounds, "steps_per_round": args.pass_steps,
+            "plain_ms_median": round(float(np.median(plain)), 4),
+            "plain_ms_spread": round(float(plain.max() - plain.min()), 4),
+            "shifted_ms_median": round(float(np.median(shifted)), 4),
+            "shifted_ms_spread": round(float(shifted.max() - shifted.min()), 4),
+            "overhead_ms_median": round(float(np.median(shifted - plain)), 4),
+            "overhead_ms_per_round": [round(float(x), 4) for x in shifted - plain],
+            "extra_algorithmic_bytes": extra,
+            "extra_ms_at_5TBps": round(extra / 5e12 * 1e3, 4),
+            "extra_launches": 4}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--m", type=int, default=2_000_000)
@@ -67,6 +116,9 @@ def main() -> int:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--time-limit", type=int, default=900, help="seconds; the run aborts past it")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--shift", action="store_true",
+                    help="time the rank-one shifted operator next to the plain one, then stop")
+    ap.add_argument("--shift-rounds", type=int, default=5)
     args = ap.parse_args()
     if args.m % 20 or args.n % 2000 or args.pass_steps < 1 or args.repeats < 1:
         ap.error("m must be a multiple of 20, n of 2000")
@@ -96,6 +148,13 @@ def main() -> int:
                "rbl_set_matrix_normal")
     out["set_matrix_normal_s"] = round(time.perf_counter() - t0, 2)
     assert svd.spmm_kernel_for(b) == _lib.RBL_SPMM_KERNEL_RECT
+
+    if args.shift:
+        out["shift"] = bench_shift(svd, indptr, indices, data, m, n, b, args)
+        svd.close()
+        signal.alarm(0)
+        print(json.dumps(out))
+        return 0
 
     # ---- each pass alone ----
     rng = np.random.default_rng(1)
