@@ -337,8 +337,27 @@ void resid_partial(int64_t nrows, int kp, const double* Z, const double* X, cons
 void copy_cols(int64_t nrows, int w, const double* src, int lds, int s0, double* dst, int ldd, int d0,
                hipStream_t s);
 
+// --- lowrank.hip -------------------------------------------------------------------------
+// The passes of the operator A + P S P^T (rbl_set_lowrank).  P: rows x rp row-major on the
+// device, rp = lr_padded_width(r) (even: 2, 4, 6, 8, 12, 16, 24 or 32; the columns past r zero;
+// 0 for r outside [1, 32]), 16-byte aligned; X, U: rows x b
+// row-major blocks, 1 <= b <= RBL_MAX_BLOCK; w, c: rp x b row-major; S: r x r row-major.
+// Fixed summation orders, no atomics; 16-byte accesses when b is even and the block is 16-byte
+// aligned, else 8-byte.
+//   lr_project: w = P^T X; part holds lr_project_grid(rows, b, rp) x rp x b doubles (the
+//               per-workgroup partials, added by reduce_slab);
+//   lr_small:   c = S w (the rows r <= i < rp of c zero), one workgroup;
+//   lr_update:  U[row][:] += P[row][:] c for row < rows — rows past `rows` are not touched.
+int lr_padded_width(int r);
+int lr_project_grid(int64_t rows, int b, int rp);
+void lr_project(int64_t rows, int b, int rp, const double* P, const double* X, double* part,
+                double* w, hipStream_t s);
+void lr_small(int r, int rp, int b, const double* S, const double* w, double* c, hipStream_t s);
+void lr_update(int64_t rows, int b, int rp, const double* P, const double* c, double* U,
+               hipStream_t s);
+
 // --- tsmm.hip ----------------------------------------------------------------------------
-// Partial Gram:  slab[s][a][c] = sum over rows of split s of W[r][a] * X[r][c]
+// Partial Gram: slab[s][a][c] = sum over rows of split s of W[r][a] * X[r][c]
 //   W: run of nW panels (a in [0, nW*w)), X: panels (c in [0, X.count*X.w)).
 // Returns the number of splits used; slab must hold splits * (nW*w) * (X.count*X.w).
 int gram_splits(int64_t nrows, int nW, int w, int xcols);

@@ -142,6 +142,17 @@ struct rbl_ctx {
   double* d_rect_ts = nullptr;
   double* d_rect_part = nullptr;
   int rect_ts_cols = 0;
+  // implicit symmetric low-rank update (rbl_set_lowrank): the operator is A + P S P^T, applied
+  // by apply_A after the SpMM.  d_lr_P: n_local x lr_rp row-major, the columns past lr_r zero
+  // (lr_rp = lr_padded_width(lr_r)); d_lr_S: r x r row-major; d_lr_wc holds w = P^T X and
+  // c = S w (lr_rp x lr_cols each), d_lr_part the workgroup partials of w; the last two are
+  // sized by ensure_lr_bufs
+  int lr_r = 0, lr_rp = 0;
+  double* d_lr_P = nullptr;
+  double* d_lr_S = nullptr;
+  double* d_lr_wc = nullptr;
+  double* d_lr_part = nullptr;
+  int lr_cols = 0;
   int64_t ntiles = 0, tiles_per_wg = 0;
   bool window_ok16 = false, window_ok32 = false;
   bool band_ok16 = false, band_ok32 = false;
@@ -1585,10 +1596,10 @@ int ensure_qext(rbl_ctx* ctx, int b, hipStream_t st) {
 // A (RBL_gpu.jl:205 with A::Matrix) the panel GEMM on fp64 MFMA (tsmm44 over the panels of
 // the local rows, Q gathered to all n rows by the halo exchange).  Returns the number of
 // A_i partials the band kernel formed in `slab` (0: none), or a negative status.
-int apply_A(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* U, const double* Qprev,
-            const double* Bi, double* slab, const double* qloc = nullptr,
-            const double* lfix_c = nullptr, double* lfix_q = nullptr, int64_t lf_lo = 0,
-            int64_t lf_hi = 0, hipEvent_t seg_wait = nullptr) {
+// This is the stored matrix alone; apply_A below adds the low-rank update when one is set.
+int apply_A_stored(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* U, const double* Qprev,
+                   const double* Bi, double* slab, const double* qloc, const double* lfix_c,
+                   double* lfix_q, int64_t lf_lo, int64_t lf_hi, hipEvent_t seg_wait) {
   if (ctx->nloc <= 0) return 0;
   if (ctx->rect) {  // B^T (B Q_i): two gather passes, the 3-term epilogue fused into the second
     CHK(ensure_rect_y(ctx, b));
@@ -1666,6 +1677,52 @@ int apply_A(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* U, cons
     transpose_small(Bi, smallp(ctx, S_BT), b, ctx->stream);
     CHK(tsmm_checked(ctx, run1(Qprev, b), smallp(ctx, S_BT), b, pan1(U, b), -1.0, 1.0, nullptr));
   }
+  return 0;
+}
+
+// the small buffers of the low-rank update for block size b: w and c (lr_rp x b each) and the
+// workgroup partials of w
+int ensure_lr_bufs(rbl_ctx* ctx, int b) {
+  if (ctx->d_lr_wc && ctx->lr_cols >= b) return RBL_OK;
+  HIPC(hipStreamSynchronize(ctx->stream));
+  hipFree(ctx->d_lr_wc);
+  hipFree(ctx->d_lr_part);
+  ctx->d_lr_wc = ctx->d_lr_part = nullptr;
+  ctx->lr_cols = 0;
+  const size_t grid = (size_t)lr_project_grid(ctx->nloc, b, ctx->lr_rp);
+  HIPC(hipMalloc(&ctx->d_lr_wc, (size_t)2 * ctx->lr_rp * b * sizeof(double)));
+  HIPC(hipMalloc(&ctx->d_lr_part, grid * ctx->lr_rp * b * sizeof(double)));
+  ctx->lr_cols = b;
+  return RBL_OK;
+}
+
+// U = Op Qin (- Qprev Bi^T), Op = A or, with an update set (rbl_set_lowrank), A + P S P^T: every
+// n-sized product of the library goes through here (rbl_apply, the block step, the Chebyshev
+// recurrences, the moment pass, the Ritz projection's W = Op V), so each sees the same operator.
+// The update runs in stream order after the SpMM, its fused 3-term epilogue and — with the local
+// reorth fused into the SpMM's staging — spmm_bt_locfix_rest, so the projection reads the final
+// Q_i:  w = P^T Q_i,  c = S w,  U[row, :] += P[row, :] c  for row < n_local (the kRowPad spare rows
+// stay as the SpMM left them).  The band kernel's A_i partials are Q_i^T U of the U before the
+// update: with an update set 0 is returned (and no partials are asked for unless the fused local
+// reorth needs that kernel), so the caller's Gram forms A_i from the final U.
+int apply_A(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* U, const double* Qprev,
+            const double* Bi, double* slab, const double* qloc = nullptr,
+            const double* lfix_c = nullptr, double* lfix_q = nullptr, int64_t lf_lo = 0,
+            int64_t lf_hi = 0, hipEvent_t seg_wait = nullptr) {
+  if (ctx->lr_r == 0 || ctx->nloc <= 0)
+    return apply_A_stored(ctx, Qin, off, b, U, Qprev, Bi, slab, qloc, lfix_c, lfix_q, lf_lo, lf_hi,
+                          seg_wait);
+  if (ctx->nranks > 1 || ctx->rect)
+    return fail(ctx, RBL_ERR_STATE, "internal: a low-rank update needs one rank and a square A");
+  CHK(ensure_lr_bufs(ctx, b));
+  const int parts = apply_A_stored(ctx, Qin, off, b, U, Qprev, Bi, lfix_c ? slab : nullptr, qloc,
+                                   lfix_c, lfix_q, lf_lo, lf_hi, seg_wait);
+  if (parts < 0) return parts;
+  const double* X = Qin + (ctx->r0 - off) * b;  // the local rows of Q_i (one rank: the block)
+  double *w = ctx->d_lr_wc, *c = ctx->d_lr_wc + (size_t)ctx->lr_rp * b;
+  lr_project(ctx->nloc, b, ctx->lr_rp, ctx->d_lr_P, X, ctx->d_lr_part, w, ctx->stream);
+  lr_small(ctx->lr_r, ctx->lr_rp, b, ctx->d_lr_S, w, c, ctx->stream);
+  lr_update(ctx->nloc, b, ctx->lr_rp, ctx->d_lr_P, c, U, ctx->stream);
   return 0;
 }
 
@@ -2364,6 +2421,16 @@ void free_rect_shift(rbl_ctx* ctx) {
   ctx->rect_shift = false;
 }
 
+// the low-rank update and the buffers of its passes
+void free_lowrank(rbl_ctx* ctx) {
+  hipFree(ctx->d_lr_P); ctx->d_lr_P = nullptr;
+  hipFree(ctx->d_lr_S); ctx->d_lr_S = nullptr;
+  hipFree(ctx->d_lr_wc); ctx->d_lr_wc = nullptr;
+  hipFree(ctx->d_lr_part); ctx->d_lr_part = nullptr;
+  ctx->lr_cols = 0;
+  ctx->lr_r = ctx->lr_rp = 0;
+}
+
 void free_matrix(rbl_ctx* ctx) {
   hipFree(ctx->d_rowptr); ctx->d_rowptr = nullptr;
   hipFree(ctx->d_col); ctx->d_col = nullptr;
@@ -2391,6 +2458,7 @@ void free_matrix(rbl_ctx* ctx) {
   for (auto& T : ctx->rect_side) free_seg(T, true);
   hipFree(ctx->d_rect_y); ctx->d_rect_y = nullptr; ctx->rect_y_cols = 0;
   free_rect_shift(ctx);
+  free_lowrank(ctx);
   ctx->rect = false;
   ctx->rect_m = 0;
   hipFree(ctx->d_dense); ctx->d_dense = nullptr;
@@ -3362,6 +3430,9 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   if (ctx->filt_deg > 0 && (ctx->rect || ctx->nranks > 1))
     return fail(ctx, RBL_ERR_INVALID, "rbl_start: a Chebyshev filter (rbl_set_filter) runs on one rank "
                                       "and a square A only");
+  if (ctx->lr_r > 0 && basis_bits != 64)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_start: a low-rank update (rbl_set_lowrank) needs the fp64 "
+                                      "basis (basis_bits = 64)");
   if (has_series(ctx) && basis_bits != 64)
     return fail(ctx, RBL_ERR_INVALID, "rbl_start: a Chebyshev series (rbl_set_filter_series) needs the "
                                       "fp64 basis (basis_bits = 64)");
@@ -4291,6 +4362,116 @@ int rbl_bench_series_pass(rbl_ctx* ctx, int64_t len, int reps, double* fused_ms,
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   if (st != RBL_OK) return fail(ctx, st, "rbl_bench_series_pass: a HIP call failed");
+  return RBL_OK;
+}
+
+// ---- implicit symmetric low-rank update: the operator A + P S P^T ---------------------------
+int rbl_set_lowrank(rbl_ctx* ctx, int r, const double* P, const double* S) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (ctx->nranks > 1)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_lowrank: one rank only (nranks > 1 is not supported)");
+  if (!has_matrix(ctx)) return fail(ctx, RBL_ERR_STATE, "rbl_set_lowrank: no matrix");
+  if (ctx->rect)
+    return fail(ctx, RBL_ERR_STATE, "rbl_set_lowrank: not with a rectangular B (rbl_set_matrix_normal; "
+                                    "its rank-one shift is rbl_set_rect_shift)");
+  HIPC(hipSetDevice(ctx->device));
+  if (r == 0 || !P) {  // clear: the operator is A again
+    HIPC(hipStreamSynchronize(ctx->stream));
+    free_lowrank(ctx);
+    ctx->cloc_step = 0;
+    return RBL_OK;
+  }
+  if (r < 1 || r > 32) return fail(ctx, RBL_ERR_INVALID, "rbl_set_lowrank: r must be in [1, 32]");
+  if (!S) return fail(ctx, RBL_ERR_INVALID, "rbl_set_lowrank: S is NULL");
+  if (ctx->d_basis32)
+    return fail(ctx, RBL_ERR_STATE, "rbl_set_lowrank: the fp64 basis only (the current run has basis_bits = 32)");
+  const int64_t n = ctx->nloc;
+  for (int64_t i = 0; i < n * r; ++i)
+    if (!std::isfinite(P[i])) return fail(ctx, RBL_ERR_INVALID, "rbl_set_lowrank: P has a non-finite entry");
+  for (int i = 0; i < r * r; ++i)
+    if (!std::isfinite(S[i])) return fail(ctx, RBL_ERR_INVALID, "rbl_set_lowrank: S has a non-finite entry");
+  for (int i = 0; i < r; ++i)
+    for (int j = 0; j < i; ++j)
+      if (S[i + (size_t)j * r] != S[j + (size_t)i * r])
+        return fail(ctx, RBL_ERR_INVALID, "rbl_set_lowrank: S is not symmetric (S[" + std::to_string(i) +
+                                              "," + std::to_string(j) + "] != S[" + std::to_string(j) + "," +
+                                              std::to_string(i) + "])");
+  // P column-major n x r -> row-major n x rp, the padding columns zero
+  const int rp = lr_padded_width(r);
+  std::vector<double> Pr((size_t)std::max<int64_t>(n, 1) * rp, 0.0);
+  for (int j = 0; j < r; ++j)
+    for (int64_t i = 0; i < n; ++i) Pr[(size_t)i * rp + j] = P[i + (size_t)j * n];
+  HIPC(hipStreamSynchronize(ctx->stream));  // steps in flight still read the old update
+  free_lowrank(ctx);
+  HIPC(hipMalloc(&ctx->d_lr_P, Pr.size() * sizeof(double)));
+  HIPC(hipMalloc(&ctx->d_lr_S, (size_t)r * r * sizeof(double)));
+  HIPC(hipMemcpy(ctx->d_lr_P, Pr.data(), Pr.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->d_lr_S, S, (size_t)r * r * sizeof(double), hipMemcpyHostToDevice));  // S = S^T
+  ctx->lr_r = r;
+  ctx->lr_rp = rp;
+  ctx->cloc_step = 0;  // the operator changes: no Gram of an earlier step carries over
+  return RBL_OK;
+}
+
+int rbl_get_lowrank(rbl_ctx* ctx, int* r, double* P_out, double* S_out) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (ctx->lr_r == 0) return fail(ctx, RBL_ERR_STATE, "rbl_get_lowrank: no update set");
+  HIPC(hipSetDevice(ctx->device));
+  if (r) *r = ctx->lr_r;
+  const int64_t n = ctx->nloc;
+  const int rr = ctx->lr_r, rp = ctx->lr_rp;
+  if (P_out) {
+    std::vector<double> Pr((size_t)std::max<int64_t>(n, 1) * rp);
+    HIPC(hipMemcpy(Pr.data(), ctx->d_lr_P, Pr.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int j = 0; j < rr; ++j)
+      for (int64_t i = 0; i < n; ++i) P_out[i + (size_t)j * n] = Pr[(size_t)i * rp + j];
+  }
+  if (S_out) HIPC(hipMemcpy(S_out, ctx->d_lr_S, (size_t)rr * rr * sizeof(double), hipMemcpyDeviceToHost));
+  return RBL_OK;
+}
+
+// Diagnostics: hipEvent time per pass of the projection w = P^T X (with its reduce_slab) and of
+// the update U += P c, on scratch blocks of rows x b (X, U) and rows x lr_padded_width(r) (P)
+// allocated and zeroed for the call.
+int rbl_bench_lowrank_pass(rbl_ctx* ctx, int64_t rows, int b, int r, int reps, double* project_ms,
+                           double* update_ms) {
+  if (!ctx || rows < 1 || b < 1 || b > RBL_MAX_BLOCK || r < 1 || r > 32 || reps < 1 || !project_ms ||
+      !update_ms)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_lowrank_pass: bad arguments");
+  HIPC(hipSetDevice(ctx->device));
+  const int rp = lr_padded_width(r);
+  const size_t grid = (size_t)lr_project_grid(rows, b, rp);
+  DevBuf x, u, p, wc, part;
+  const std::pair<DevBuf*, size_t> bufs[] = {{&x, (size_t)rows * b},
+                                             {&u, (size_t)rows * b},
+                                             {&p, (size_t)rows * rp},
+                                             {&wc, (size_t)2 * rp * b},
+                                             {&part, grid * rp * b}};
+  for (const auto& q : bufs) {
+    HIPC(hipMalloc(&q.first->p, q.second * sizeof(double)));
+    HIPC(hipMemsetAsync(q.first->p, 0, q.second * sizeof(double), ctx->stream));
+  }
+  double *w = wc.d(), *c = wc.d() + (size_t)rp * b;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  auto project = [&] { lr_project(rows, b, rp, p.d(), x.d(), part.d(), w, ctx->stream); };
+  auto update = [&] { lr_update(rows, b, rp, p.d(), c, u.d(), ctx->stream); };
+  int st = RBL_OK;
+  auto timed = [&](auto&& fn, double* out) {
+    fn();  // warm-up
+    if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+    for (int q = 0; q < reps; ++q) fn();
+    if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+    *out = (double)ms / reps;
+  };
+  timed(project, project_ms);
+  timed(update, update_ms);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_lowrank_pass: a HIP call failed");
   return RBL_OK;
 }
 

@@ -5,7 +5,9 @@ images.jl:20-33 on the implicit B^T B (``shift=(u, v)``: of B - u v^T), ``RBL_pc
 sparse B with implicit centring on top of it, ``RBL_filtered(A, k, b, which="SA"|"LA")`` the smallest or
 largest eigenpairs through a Chebyshev filter, ``RBL_interior(A, k, b, sigma)`` the eigenpairs
 nearest sigma through a Chebyshev delta series, ``RBL_interval(A, (x0, x1), b)`` all eigenpairs in
-an interval (``spectral_density`` / ``eig_count``: the Chebyshev moments behind it); ``Context`` wraps the C-ABI of
+an interval (``spectral_density`` / ``eig_count``: the Chebyshev moments behind it); each of the
+square-A drivers takes ``update=(P, S)`` for the implicit operator A + P S P^T (``rbl.lowrank``:
+``modularity_update``, ``deflation_update``, ``centering_update``, ``RBL_modularity``); ``Context`` wraps the C-ABI of
 librbl_hip.so (include/rbl_hip.h).  Importing this package loads the HIP library and fails
 loudly if it has not been built: there is no CPU fallback.
 """
@@ -22,3 +24,5 @@ from .interior import (RBL_interior, delta_coeffs, estimate_spectrum, lanczos_in
                        series_eval, spectrum_bounds)
 from .density import (RBL_interval, check_moments, eig_count, interval_degree, interval_run,  # noqa: F401
                       jackson, kpm_count, kpm_density, spectral_density)
+from .lowrank import (RBL_modularity, centering_update, deflation_update,  # noqa: F401
+                      modularity_update)

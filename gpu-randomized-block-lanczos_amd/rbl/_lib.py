@@ -109,6 +109,9 @@ SIGNATURES = {
     "rbl_bench_series_pass": (C.c_int, [_p, _i64, C.c_int, _pd, _pd]),
     "rbl_cheb_moments": (C.c_int, [_p, C.c_int, C.c_int, C.c_double, C.c_double, _pd, _u64, _pd]),
     "rbl_bench_moment_pass": (C.c_int, [_p, _i64, C.c_int, C.c_int, _pd]),
+    "rbl_set_lowrank": (C.c_int, [_p, C.c_int, _pd, _pd]),
+    "rbl_get_lowrank": (C.c_int, [_p, C.POINTER(C.c_int), _pd, _pd]),
+    "rbl_bench_lowrank_pass": (C.c_int, [_p, _i64, C.c_int, C.c_int, C.c_int, _pd, _pd]),
     "rbl_ritz_project": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd]),
     "rbl_ritz_finish": (C.c_int, [_p, C.c_int, _pd, _pd, _pd, _pd]),
     "rbl_ritz_finish_cols": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd, _pd, _pd]),

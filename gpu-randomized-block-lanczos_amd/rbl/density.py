@@ -30,7 +30,7 @@ import numpy as np
 
 from . import _lib
 from .interior import HALF_WIDTH_C, estimate_spectrum, half_width, jackson, lanczos_interior  # noqa: F401
-from .rbl_gpu import KRYL_SZ_GPU, RESIDUAL_TOL, Context
+from .rbl_gpu import KRYL_SZ_GPU, RESIDUAL_TOL, Context, set_update
 
 # |m_j| <= m_0 when [lo, hi] encloses the spectrum; the slack covers the rounding of the dots
 MOMENT_BOUND_SLACK = 1e-8
@@ -172,7 +172,7 @@ def _moments_run(ctx: Context, nvec: int, degree: int, bounds, seed: int):
 
 
 def spectral_density(A, x, *, nvec: int = 32, degree: int = 100, bounds=None, seed: int = 0,
-                     device: int = 0):
+                     device: int = 0, update=None):
     """The density of states of the symmetric A (SciPy sparse or dense NumPy) at the points x from
     2 degree + 1 Chebyshev moments over nvec N(0,1) vectors (`degree` SpMMs of block nvec).
     bounds: (lo, hi) enclosing the whole spectrum; None estimates them (estimate_spectrum, widened
@@ -180,13 +180,14 @@ def spectral_density(A, x, *, nvec: int = 32, degree: int = 100, bounds=None, se
     Returns (phi, info); info holds "bounds", "moments", "nvec", "degree".  One GPU."""
     with Context(device) as ctx:
         ctx.set_matrix(A)
+        set_update(ctx, update)    # update=(P, S): of A + P S P^T (Context.set_lowrank)
         mom, info = _moments_run(ctx, nvec, degree, bounds, seed)
     lo, hi = info["bounds"]
     return kpm_density(mom, lo, hi, x), info
 
 
 def eig_count(A, x0: float, x1: float, *, nvec: int = 32, degree: int = 100, bounds=None,
-              seed: int = 0, device: int = 0):
+              seed: int = 0, device: int = 0, update=None):
     """The expected number of eigenvalues of the symmetric A in [x0, x1] (kpm_count) from
     2 degree + 1 Chebyshev moments over nvec N(0,1) vectors.  Returns (count, info) as
     spectral_density."""
@@ -194,6 +195,7 @@ def eig_count(A, x0: float, x1: float, *, nvec: int = 32, degree: int = 100, bou
         raise ValueError("eig_count: needs x0 <= x1")
     with Context(device) as ctx:
         ctx.set_matrix(A)
+        set_update(ctx, update)    # update=(P, S): of A + P S P^T (Context.set_lowrank)
         mom, info = _moments_run(ctx, nvec, degree, bounds, seed)
     lo, hi = info["bounds"]
     return kpm_count(mom, lo, hi, x0, x1), info
@@ -257,12 +259,14 @@ def interval_run(ctx: Context, interval, b: int, *, nvec: int = 32, count_degree
 
 def RBL_interval(A, interval, b: int, *, nvec: int = 32, count_degree: int = 100, slack: float = 1.25,
                  width_factor: float = 4.0, bounds=None, max_rounds: int = 3, device: int = 0,
-                 omega=None, seed: int = 0, tol: float = RESIDUAL_TOL, kryl_sz: int = KRYL_SZ_GPU):
+                 omega=None, seed: int = 0, tol: float = RESIDUAL_TOL, kryl_sz: int = KRYL_SZ_GPU,
+                 update=None):
     """All eigenpairs of the symmetric A (SciPy sparse or dense NumPy) with x0 <= lambda <= x1,
     interval = (x0, x1), ascending — the calling convention of EVSL and FEAST — from a KPM count
     and Chebyshev-filtered block Lanczos.  Returns (D, V, info); see ``interval_run``."""
     with Context(device) as ctx:
         ctx.set_matrix(A)
+        set_update(ctx, update)    # update=(P, S): of A + P S P^T (Context.set_lowrank)
         return interval_run(ctx, interval, b, nvec=nvec, count_degree=count_degree, slack=slack,
                             width_factor=width_factor, bounds=bounds, max_rounds=max_rounds, omega=omega,
                             seed=seed, tol=tol, kryl_sz=kryl_sz)

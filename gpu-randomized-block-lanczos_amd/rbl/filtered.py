@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from .host import TBand, dsbev, fix_signs, sort_eig_abs
-from .rbl_gpu import KRYL_SZ_GPU, RESIDUAL_TOL, Context, lanczos
+from .rbl_gpu import KRYL_SZ_GPU, RESIDUAL_TOL, Context, lanczos, set_update
 
 
 def cheb_scalars(degree: int, lo: float, hi: float, ref: float):
@@ -162,11 +162,14 @@ def lanczos_filtered(ctx: Context, k: int, b: int, *, which: str = "SA", degree:
 
 def RBL_filtered(A, k: int, b: int, *, which: str = "SA", degree: int = 8, bounds=None,
                  device: int = 0, kryl_sz: int = KRYL_SZ_GPU, omega=None, seed: int = 0,
-                 tol: float = RESIDUAL_TOL, max_steps: "int | None" = None, trace: bool = False):
+                 tol: float = RESIDUAL_TOL, max_steps: "int | None" = None, trace: bool = False,
+                 update=None):
     """The k algebraically smallest (which="SA") or largest ("LA") eigenpairs of the symmetric A
     (SciPy sparse or dense NumPy) — scipy.sparse.linalg.eigsh's `which` — through a degree-
-    `degree` Chebyshev filter.  Returns (D, V, info); see ``lanczos_filtered``."""
+    `degree` Chebyshev filter.  Returns (D, V, info); see ``lanczos_filtered``.  update=(P, S): of
+    A + P S P^T (Context.set_lowrank), the bounds estimated on that operator."""
     with Context(device) as ctx:
         ctx.set_matrix(A)
+        set_update(ctx, update)
         return lanczos_filtered(ctx, k, b, which=which, degree=degree, bounds=bounds, kryl_sz=kryl_sz,
                         omega=omega, seed=seed, tol=tol, max_steps=max_steps, trace=trace)

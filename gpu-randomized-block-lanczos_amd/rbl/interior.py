@@ -27,7 +27,7 @@ import numpy as np
 from . import _lib
 from .filtered import _t_eig
 from .host import fix_signs, sort_eig_abs
-from .rbl_gpu import KRYL_SZ_GPU, RESIDUAL_TOL, Context, lanczos
+from .rbl_gpu import KRYL_SZ_GPU, RESIDUAL_TOL, Context, lanczos, set_update
 
 # lambda-distance from sigma at which p = 1/2 is e sin(theta_sigma) HALF_WIDTH_C / (d + 2)
 # (measured on the kernel itself for d from 50 to 1000; tests/test_interior_host.py holds it to 1 %)
@@ -198,12 +198,13 @@ def lanczos_interior(ctx: Context, k: int, b: int, sigma: float, *, degree: int 
 def RBL_interior(A, k: int, b: int, sigma: float, *, degree: int = 100, bounds=None,
                  extra: "int | None" = None, device: int = 0, omega=None, seed: int = 0,
                  tol: float = RESIDUAL_TOL, kryl_sz: int = KRYL_SZ_GPU,
-                 max_steps: "int | None" = None, trace: bool = False):
+                 max_steps: "int | None" = None, trace: bool = False, update=None):
     """The k eigenpairs of the symmetric A (SciPy sparse or dense NumPy) nearest sigma —
     scipy.sparse.linalg.eigsh's `sigma` — through a degree-`degree` Chebyshev delta filter.
     Returns (D, V, info); see ``lanczos_interior``."""
     with Context(device) as ctx:
         ctx.set_matrix(A)
+        set_update(ctx, update)    # update=(P, S): the eigenpairs of A + P S P^T nearest sigma
         return lanczos_interior(ctx, k, b, sigma, degree=degree, bounds=bounds, extra=extra,
                                 omega=omega, seed=seed, tol=tol, kryl_sz=kryl_sz,
                                 max_steps=max_steps, trace=trace)

@@ -238,6 +238,55 @@ class Context:
                                                dptr(Y)), "rbl_apply_rect_shifted")
         return Y
 
+    # -- implicit symmetric low-rank update: the operator A + P S P^T ------------------------
+    def set_lowrank(self, P, S) -> None:
+        """The operator becomes A + P S P^T (rbl_set_lowrank): P n x r, S r x r symmetric,
+        1 <= r <= 32, both copied to the device; a 1-D P with a scalar S is r = 1; ``None, None``
+        clears the update.  While set, apply / start / step / the Chebyshev filters / cheb_moments /
+        ritz_project run on the updated operator.  Square A, one rank, fp64 basis."""
+        if P is None and S is None:
+            self._check(lib.rbl_set_lowrank(self._h, 0, None, None), "rbl_set_lowrank")
+            return
+        if P is None or S is None:
+            raise ValueError("set_lowrank: P and S must both be given or both be None")
+        n, r0, r1, _ = self.matrix_info()
+        P = np.asarray(P, dtype=np.float64)
+        S = np.asarray(S, dtype=np.float64)
+        if P.ndim == 1:
+            P = P.reshape(-1, 1)
+        if S.ndim == 0:
+            S = S.reshape(1, 1)
+        if P.ndim != 2 or P.shape[0] != r1 - r0:
+            raise ValueError(f"set_lowrank: P must have {r1 - r0} rows")
+        r = P.shape[1]
+        if S.shape != (r, r):
+            raise ValueError(f"set_lowrank: S must be {r} x {r}")
+        if r < 1:
+            raise ValueError("set_lowrank: P has no columns (None, None clears the update)")
+        P = np.asfortranarray(P)
+        S = np.asfortranarray(S)
+        self._check(lib.rbl_set_lowrank(self._h, r, dptr(P), dptr(S)), "rbl_set_lowrank")
+
+    def get_lowrank(self):
+        """(P, S) of the update set (rbl_get_lowrank), exactly as passed: P n x r, S r x r;
+        RBLError (RBL_ERR_STATE) when none is."""
+        import ctypes as C
+        r = C.c_int(0)
+        self._check(lib.rbl_get_lowrank(self._h, C.byref(r), None, None), "rbl_get_lowrank")
+        n, r0, r1, _ = self.matrix_info()
+        P = np.zeros((r1 - r0, r.value), order="F")
+        S = np.zeros((r.value, r.value), order="F")
+        self._check(lib.rbl_get_lowrank(self._h, C.byref(r), dptr(P), dptr(S)), "rbl_get_lowrank")
+        return P, S
+
+    def bench_lowrank_pass(self, rows: int, b: int, r: int, reps: int = 10):
+        """(project_ms, update_ms) per pass of the two n-sized passes of the low-rank update on
+        scratch blocks (rbl_bench_lowrank_pass)."""
+        pm, um = np.zeros(1), np.zeros(1)
+        self._check(lib.rbl_bench_lowrank_pass(self._h, int(rows), int(b), int(r), int(reps), dptr(pm),
+                                               dptr(um)), "rbl_bench_lowrank_pass")
+        return float(pm[0]), float(um[0])
+
     def left_vectors(self, V: np.ndarray, sigma) -> np.ndarray:
         """U = B V diag(1 / sigma) (images.jl:24), m x k, from V (n x k) and the singular values
         (with a shift set: C V diag(1 / sigma))."""
@@ -558,6 +607,18 @@ def rccl_version() -> dict:
             "rccl_version_code": code, "rccl_path": buf.value.decode()}
 
 
+def set_update(ctx: Context, update) -> None:
+    """The ``update=(P, S)`` keyword of the drivers: the operator A + P S P^T, set straight after
+    the matrix (so bound estimation sees the updated operator); None: the plain A."""
+    if update is None:
+        return
+    try:
+        P, S = update
+    except (TypeError, ValueError):
+        raise ValueError("update must be a pair (P, S)") from None
+    ctx.set_lowrank(P, S)
+
+
 def max_steps_for(kryl_sz: int, b: int) -> int:
     """Number of block steps the loop `while i*b < kryl_sz` can run (RBL_gpu.jl:162)."""
     return max(1, math.ceil(kryl_sz / b))
@@ -695,13 +756,16 @@ def lanczos(ctx: Context, k: int, b: int, *, kryl_sz: int = KRYL_SZ_GPU, omega=N
 
 def RBL_gpu(A, k: int, b: int, *, device: int = 0, kryl_sz: int = KRYL_SZ_GPU, omega=None,
             seed: int = 0, reorth_order: int = 0, return_info: bool = False, basis_bits: int = 64,
-            device_blocks: int = 0):
+            device_blocks: int = 0, update=None):
     """Drop-in for ``RBL_gpu(A::SparseMatrixCSC{Float64}, k, b)`` (RBL_gpu.jl:205):
     returns (D, V) — D the k largest-|lambda| eigenvalues (descending |lambda|), V n x k.
     device_blocks: Krylov blocks kept in HBM (RBL_OPT_DEVICE_BLOCKS: 0 all, -1 what fits —
-    the reference's gpu_buffer_size — or G >= 3; older blocks spill to pinned host memory)."""
+    the reference's gpu_buffer_size — or G >= 3; older blocks spill to pinned host memory).
+    update=(P, S): the eigenpairs of A + P S P^T, never formed (Context.set_lowrank; rbl.lowrank
+    builds the usual ones; fp64 basis)."""
     with Context(device) as ctx:
         ctx.set_matrix(A)
+        set_update(ctx, update)
         ctx.set_option(_lib.RBL_OPT_REORTH_ORDER, reorth_order)
         ctx.set_option(_lib.RBL_OPT_DEVICE_BLOCKS, device_blocks)
         D, V, info = lanczos(ctx, k, b, kryl_sz=kryl_sz, omega=omega, seed=seed,

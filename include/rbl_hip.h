@@ -311,7 +311,8 @@ int rbl_row_ids(rbl_ctx* ctx, int64_t* ids);
 int rbl_get_matrix_csr(rbl_ctx* ctx, int64_t* rowptr, int32_t* colind, double* val);
 /* Y = A X for a host n_local x b column-major block (the operator of RBL_gpu.jl:176,
  * `mul!(U, Ag, Qg_d)`), through the same SpMM kernels as rbl_step (multi-rank: with the
- * halo exchange).  Allocates its own device buffers. */
+ * halo exchange); with an update set (rbl_set_lowrank) Y = (A + P S P^T) X.  Allocates its own
+ * device buffers. */
 int rbl_apply(rbl_ctx* ctx, int b, const double* X, double* Y);
 /* Which SpMM kernel rbl_step / rbl_apply use for block size b under the current option:
  * 1 = global-gather CSR, 2 = LDS-window CSR (DPP), 3 = LDS-densified band on fp64 MFMA,
@@ -426,9 +427,47 @@ int rbl_cheb_moments(rbl_ctx* ctx, int b, int degree, double lo, double hi, cons
  * row pass of a middle term with its partial-sum reduction, over blocks of len_rows x b doubles
  * allocated for the call. */
 int rbl_bench_moment_pass(rbl_ctx* ctx, int64_t len_rows, int b, int reps, double* ms);
+
+/* ---- implicit symmetric low-rank update: the operator A + P S P^T ----------------------------
+ * (No reference equivalent.)  rbl_set_lowrank: with P (n x r, host, column-major) and S (r x r,
+ * host, column-major, symmetric) every later n-sized product of the library runs on
+ *     Op = A + P S P^T
+ * — the modularity matrix A - d d^T / (2m) (r = 1), Hotelling deflation A - V Theta V^T past the
+ * eigenpairs already found, a double-centred kernel matrix H K H (r = 2, S not diagonal) — which
+ * is dense and never formed.  All of them go through one operator routine, so rbl_apply,
+ * rbl_start, rbl_step, rbl_step_async, the restarted entry points, both Chebyshev filters
+ * (rbl_apply_filter: p(Op)), rbl_cheb_moments and rbl_ritz_project / rbl_ritz_finish (W = Op V,
+ * residuals ||Op v - theta v||) all see Op.  After the SpMM and its fused 3-term epilogue three
+ * passes run in stream order, with no host round trip:
+ *     w = P^T X (r x b),   c = S w,   U[row, :] += P[row, :] c   (rows < n_local)
+ * every sum in a fixed order (no atomics): two calls give the same bits.  P and S are copied (P
+ * to n x rp doubles on the device, rp = r rounded up to one of 2, 4, 6, 8, 12, 16, 24, 32); the
+ * caller's arrays are not kept.  Set it before rbl_start: a run in flight is waited for, and its
+ * basis belongs to the operator it was built with.  A block step forms A_i = Q_i^T U from the
+ * final U with its own Gram (the band-tile kernel's fused A_i partials predate the update).
+ * r = 0 or P = NULL clears the update: results are then bit for bit those of a context that never
+ * had one, with no extra launch.  Setting any matrix clears it too.
+ * Limits, each checked before any allocation, the context and an earlier update staying as they
+ * were: RBL_ERR_STATE without a matrix, with a rectangular B (rbl_set_matrix_normal) or while the
+ * current run has the fp32 basis; RBL_ERR_INVALID on a context with several ranks, for r outside
+ * [1, 32], S = NULL, a non-finite entry of P or S, or S != S^T (compared exactly); rbl_start with
+ * basis_bits = 32 while an update is set returns RBL_ERR_INVALID.  Dense and sparse A, any
+ * b <= RBL_MAX_BLOCK.  Extra device memory: n x rp x 8 B and under 8 workgroups per CU x rp x b x 8 B. */
+int rbl_set_lowrank(rbl_ctx* ctx, int r, const double* P, const double* S);
+/* The update set: *r_out its rank, P_out (n x r) and S_out (r x r) column-major, exactly the
+ * values passed (any of the three may be NULL; call once for r, then with buffers).
+ * RBL_ERR_STATE when no update is set. */
+int rbl_get_lowrank(rbl_ctx* ctx, int* r_out, double* P_out, double* S_out);
+/* Diagnostics: the time per pass (ms, hipEvents, mean over `reps` after one warm-up) of the
+ * projection w = P^T X (its partial-sum reduction included) and of the update U += P c, over
+ * scratch blocks of rows x b doubles and a rows x r factor allocated for the call. */
+int rbl_bench_lowrank_pass(rbl_ctx* ctx, int64_t rows, int b, int r, int reps, double* project_ms,
+                           double* update_ms);
+
 /* Rayleigh-Ritz on A with true residuals (also without a filter).
  * rbl_ritz_project: V = [Q_1..Q_nblocks] S (S: (nblocks*b) x k column-major, host; orthonormal
- *   columns) and W = A V (the plain operator) are formed and kept on the device; H_out (k x k
+ *   columns) and W = A V (the plain operator, never the filter; with rbl_set_lowrank A + P S P^T)
+ *   are formed and kept on the device; H_out (k x k
  *   column-major, host) = V^T W.  k <= RBL_MAX_BLOCK; one rank; replaces an earlier projection.
  * rbl_ritz_finish: with the host's eigendecomposition H = Y diag(theta) Y^T (Y: k x k
  *   column-major), V_out (n_local x k column-major) = V Y and resid_out[j] =

@@ -16,6 +16,8 @@
 #   D, V = RBL_hip_restarted(A, k)       # restarted.jl:106 (RBL_gpu_restarted)
 #   U, D, V = RBL_gpu_svd(B, k, b)       # images.jl:29-33 on a sparse rectangular B, B^T B implicit
 #   U, D, V, mu = RBL_gpu_pca(B, k, b)  # PCA of a sparse B: the triplets of B - 1 mu^T, never formed
+#   D, V = RBL_hip(A, k, b; update = (P, S))   # the operator A + P S P^T, never formed
+#   D, V = RBL_gpu_deflated(A, k, b, V0, D0)   # the next k pairs after (D0, V0): A - V0 diag(D0) V0'
 #   D, V, r = RBL_gpu_filtered(A, k, b; which = :SA, degree = 8)   # the k smallest (or :LA largest)
 #                                        # pairs through a Chebyshev filter, r = ||A v - D v||
 #   c, (lo, hi) = RBL_gpu_eigcount(A, x0, x1)     # expected number of eigenvalues in [x0, x1] (KPM)
@@ -85,6 +87,18 @@ function set_rect_shift!(ctx, u::Vector{Float64}, v::Vector{Float64})
                          (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx, u, v), "rbl_set_rect_shift")
 end
 
+# The implicit symmetric low-rank update of the square A held (rbl_set_lowrank): P n x r, S r x r
+# symmetric, 1 <= r <= 32, both column-major as Julia stores them and copied to the device.  Every
+# later product (rbl_start, rbl_step*, rbl_apply, the filters, rbl_ritz_project) runs on
+# A + P S P^T.  One rank, fp64 basis.
+function set_lowrank!(ctx, P::Matrix{Float64}, S::Matrix{Float64})
+    size(S, 1) == size(S, 2) == size(P, 2) ||
+        throw(ArgumentError("set_lowrank!: P must be n x r and S r x r"))
+    rbl_check(ctx, ccall((:rbl_set_lowrank, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}),
+                         ctx, Cint(size(P, 2)), P, S), "rbl_set_lowrank")
+end
+
 function rbl_context(device::Int)
     hr = Ref{Ptr{Cvoid}}(C_NULL)
     st = ccall((:rbl_create, librbl_hip), Cint, (Ref{Ptr{Cvoid}}, Cint), hr, Cint(device))
@@ -120,7 +134,7 @@ end
 function RBL_hip(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k::Int64, b::Int64;
                  device::Int = 0, seed::UInt64 = rand(UInt64), kryl_sz::Int64 = 1200,
                  basis_bits::Int = (FLOAT == Float32 ? 32 : 64), device_blocks::Int = 0,
-                 timer = nothing, normal::Bool = false, shift = nothing)
+                 timer = nothing, normal::Bool = false, shift = nothing, update = nothing)
     # normal: A is a rectangular B and the operator B^T B (RBL_gpu_svd); then the left singular
     # vectors are formed before the context is released and returned as a third value
     # shift = (u, v) (normal only): the operator is C^T C, C = B - u v^T (RBL_gpu_pca)
@@ -129,11 +143,14 @@ function RBL_hip(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k::Int64, b
         length(shift[1]) == size(A, 1) && length(shift[2]) == size(A, 2) ||
             throw(ArgumentError("RBL_hip: shift = (u, v) needs length(u) = size(A, 1), length(v) = size(A, 2)"))
     end
+    # update = (P, S) (square A only): the operator is A + P S P^T (rbl_set_lowrank; fp64 basis)
+    update === nothing || !normal || throw(ArgumentError("RBL_hip: update needs a square A (normal = false)"))
     n = size(A, 2)
     ctx = rbl_context(device)
     try
         normal ? set_matrix_normal!(ctx, A) : set_matrix!(ctx, A)
         shift === nothing || set_rect_shift!(ctx, Vector{Float64}(shift[1]), Vector{Float64}(shift[2]))
+        update === nothing || set_lowrank!(ctx, Matrix{Float64}(update[1]), Matrix{Float64}(update[2]))
         # RBL_OPT_DEVICE_BLOCKS: the hybrid GPU/host Krylov buffer (RBL_gpu.jl:24-27, 59-81)
         rbl_check(ctx, ccall((:rbl_set_option, librbl_hip), Cint, (Ptr{Cvoid}, Cint, Int64),
                              ctx, RBL_OPT_DEVICE_BLOCKS, device_blocks), "rbl_set_option")
@@ -284,6 +301,19 @@ function RBL_gpu_pca(B::SparseMatrixCSC{DOUBLE}, k::Int64, b::Int64)
     D, V, U = RBL_hip(B, k, b; timer = timer, normal = true, basis_bits = 64,
                       shift = (ones(Float64, m), mu))
     return U, D, V, mu
+end
+
+# Hotelling deflation: the k largest-magnitude eigenpairs of A - V0 diag(D0) V0', i.e. the pairs of
+# A after the ones already found (D0, V0 from an earlier RBL_gpu run; at most 32 of them), through
+# the low-rank update (V0, -diag(D0)).  The deflated matrix, which is dense, is never formed.
+function RBL_gpu_deflated(A::Union{SparseMatrixCSC{DOUBLE},Matrix{DOUBLE}}, k::Int64, b::Int64,
+                          V0::Matrix{Float64}, D0::Vector{Float64})
+    timer = isdefined(Main, :to) ? Main.to : nothing
+    S = zeros(Float64, length(D0), length(D0))
+    for j in 1:length(D0)
+        S[j, j] = -D0[j]
+    end
+    return RBL_hip(A, k, b; timer = timer, basis_bits = 64, update = (V0, S))
 end
 
 # restarted.jl:106-146 (RBL_gpu_restarted): b = 1 cycles with locking.  The cycle
