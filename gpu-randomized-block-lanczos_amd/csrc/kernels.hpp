@@ -327,6 +327,22 @@ int moment_grid(int64_t nrows, int b);
 void cheb_moment_term(int64_t nrows, int b, const double* W, const double* T1, const double* T2,
                       double alpha, double beta, double* Tout, double* part, int grid, bool first,
                       bool last, hipStream_t s);
+// One term of the diagonal recurrence (rbl_cheb_diag) after its SpMM W = A t_{j-1} (n x b
+// row-major blocks, 1 <= b <= 256: a row is finished inside one tile pass of the workgroup, so no
+// cross-chunk row accumulation exists; a wider b is not launched):
+//   t_j = alpha W + beta T1 (- T2 unless first), stored to Tout unless last (Tout may be W);
+//   s[row] = sum_c X[row][c] t_j[row][c];   D[row][e] += coef[e] s[row], e < nf (D: n x nf row-major,
+//   coef: this term's nf coefficients, on the device);
+//   first (T1 = X; T1, T2 not read; coef: the 2 nf coefficients of terms 0 and 1): q[row] = sum_c
+//   X[row][c]^2, qout[row] = q, D[row][e] = coef[e] q + coef[nf + e] s (D not read).
+// The row sums run in a fixed order (each thread its slot's columns, the row's slots ascending
+// through LDS, one owner thread per element of D): no atomics, two calls give the same bits.
+// 16-byte accesses when b is even and every pointer used is 16-byte aligned, else 8-byte.
+void cheb_diag_term(int64_t nrows, int b, int nf, const double* W, const double* T1, const double* T2,
+                    const double* X, double alpha, double beta, double* Tout, const double* coef,
+                    double* D, double* qout, bool first, bool last, hipStream_t s);
+// x[i] = x[i] < 0 ? -1 : +1 in place over `len` doubles (0 -> +1): the signs of an N(0,1) block
+void sign_block(int64_t len, double* x, hipStream_t s);
 // part[g][c] = sum over workgroup g's rows of (Z[r][c] - X[r][c] theta[c])^2, c < kp (Z, X: n x kp
 // row-major), g < grid = resid_grid(nrows): a fixed summation order, no atomics; reduce_slab
 // over the grid gives the squared column norms.

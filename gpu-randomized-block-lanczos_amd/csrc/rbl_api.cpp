@@ -4598,6 +4598,127 @@ int rbl_bench_moment_pass(rbl_ctx* ctx, int64_t len_rows, int b, int reps, doubl
   return RBL_OK;
 }
 
+// ---- diagonals of Chebyshev series (matrix functions) ----------------------------------------
+// num[row][e] = sum_c x_c[row] (p_e(Op) x_c)[row], p_e = sum_j coef[j][e] T_j((Op - cI)/e), and
+// den[row] = sum_c x_c[row]^2, from `degree` SpMMs for all nf series: the recurrence and scalars of
+// rbl_cheb_moments, each term followed by ONE cheb_diag_term that forms t_j, the row sums of X o t_j
+// and the nf updates of D.  The blocks are the call's own: X stays in xb (the rotation of the three
+// work blocks overwrites t_0's slot at term 3, and every term reads X); t_j lives in f[j % 3].
+int rbl_cheb_diag(rbl_ctx* ctx, int b, int degree, double lo, double hi, int nf, const double* coef,
+                  const double* X, uint64_t seed, int probe, double* num_out, double* den_out) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (b < 1 || b > 256) return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: b must be in [1, 256]");
+  if (degree < 1 || degree > 65535)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: degree must be in [1, 65535]");
+  if (nf < 1 || nf > 32) return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: nf must be in [1, 32]");
+  if (!std::isfinite(lo) || !std::isfinite(hi))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: lo and hi must be finite");
+  if (!(lo < hi)) return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: needs lo < hi");
+  if (!coef) return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: coef is NULL");
+  if (probe != RBL_PROBE_GAUSS && probe != RBL_PROBE_SIGN)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: probe must be RBL_PROBE_GAUSS or RBL_PROBE_SIGN");
+  if (!num_out || !den_out) return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: num_out or den_out is NULL");
+  const size_t ncoef = (size_t)(degree + 1) * nf;
+  for (size_t i = 0; i < ncoef; ++i)
+    if (!std::isfinite(coef[i])) return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: coef has a non-finite entry");
+  if (ctx->nranks > 1)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: one rank only (nranks > 1 is not supported)");
+  if (!has_matrix(ctx)) return fail(ctx, RBL_ERR_STATE, "rbl_cheb_diag: no matrix");
+  if (ctx->rect)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: not with a rectangular B (rbl_set_matrix_normal)");
+  HIPC(hipSetDevice(ctx->device));
+  const int64_t n = ctx->nloc, nl = std::max<int64_t>(n, 1);
+  const size_t padded = (size_t)(nl + kRowPad) * b * sizeof(double);
+  // term-major on the device: term j's nf coefficients contiguous
+  std::vector<double> cj(ncoef);
+  for (int e = 0; e < nf; ++e)
+    for (int j = 0; j <= degree; ++j) cj[(size_t)j * nf + e] = coef[(size_t)e * (degree + 1) + j];
+  DevBuf f[3], xb, dd, dcm, dq, dcoef;
+  for (DevBuf* p : {&f[0], &f[1], &f[2], &xb}) {
+    HIPC(hipMalloc(&p->p, padded));
+    HIPC(hipMemsetAsync(p->p, 0, padded, ctx->stream));
+  }
+  HIPC(hipMalloc(&dd.p, (size_t)nl * nf * sizeof(double)));
+  HIPC(hipMalloc(&dcm.p, (size_t)nl * nf * sizeof(double)));
+  HIPC(hipMalloc(&dq.p, (size_t)nl * sizeof(double)));
+  HIPC(hipMalloc(&dcoef.p, ncoef * sizeof(double)));
+  HIPC(hipMemcpyAsync(dcoef.p, cj.data(), ncoef * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (X) {  // column-major through f[1], which the first SpMM overwrites
+    HIPC(hipMemcpyAsync(f[1].p, X, n * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    colmajor_to_rowmajor(f[1].d(), n, b, xb.d(), ctx->stream);
+  } else {
+    randn_block(xb.d(), n, b, ctx->r0, seed, ctx->stream, ctx->relabeled ? &ctx->relabel_perm : nullptr);
+    if (probe == RBL_PROBE_SIGN) sign_block(n * b, xb.d(), ctx->stream);
+  }
+  HIPC(hipGetLastError());
+  const double c = 0.5 * (lo + hi), e = 0.5 * (hi - lo);
+  {
+    StageScope t(ctx, RBL_STAGE_AQ);
+    const double* t1 = xb.d();   // t_{j-1}
+    const double* t2 = nullptr;  // t_{j-2}
+    for (int j = 1; j <= degree; ++j) {
+      double* tj = f[j % 3].d();
+      const int st = apply_A(ctx, t1, 0, b, tj, nullptr, nullptr, nullptr);
+      if (st < 0) return st;
+      const double al = (j == 1 ? 1.0 : 2.0) / e;
+      const double* cf = dcoef.d() + (j == 1 ? 0 : (size_t)j * nf);
+      cheb_diag_term(n, b, nf, tj, t1, t2, xb.d(), al, -al * c, tj, cf, dd.d(), dq.d(), j == 1, j == degree,
+                     ctx->stream);
+      HIPC(hipGetLastError());
+      t2 = t1;
+      t1 = tj;
+    }
+  }
+  rowmajor_to_colmajor(dd.d(), n, nf, dcm.d(), ctx->stream);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(num_out, dcm.p, n * nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(den_out, dq.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  harvest_timers(ctx);
+  return RBL_OK;
+}
+
+// Diagnostics (tools/bench_funm.py): hipEvent time per pass of the diagonal pass (a middle term:
+// reads W, t_{j-1}, t_{j-2}, X; writes t_j over W; read-modify-write of D) on blocks of
+// len_rows x b doubles and a len_rows x nf D.  The coefficients keep the values bounded over any
+// number of repeats.
+int rbl_bench_diag_pass(rbl_ctx* ctx, int64_t len_rows, int b, int nf, int reps, double* ms) {
+  if (!ctx || len_rows < 1 || b < 1 || b > 256 || nf < 1 || nf > 32 || reps < 1 || !ms)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_diag_pass: bad arguments");
+  HIPC(hipSetDevice(ctx->device));
+  DevBuf w, t1, t2, x, dd, dq, dcoef;
+  const size_t bytes = (size_t)len_rows * b * sizeof(double);
+  for (DevBuf* p : {&w, &t1, &t2, &x}) {
+    HIPC(hipMalloc(&p->p, bytes));
+    HIPC(hipMemsetAsync(p->p, 0, bytes, ctx->stream));
+  }
+  HIPC(hipMalloc(&dd.p, (size_t)len_rows * nf * sizeof(double)));
+  HIPC(hipMemsetAsync(dd.p, 0, (size_t)len_rows * nf * sizeof(double), ctx->stream));
+  HIPC(hipMalloc(&dq.p, (size_t)len_rows * sizeof(double)));
+  HIPC(hipMalloc(&dcoef.p, (size_t)nf * sizeof(double)));
+  const std::vector<double> cf((size_t)nf, 1e-3);
+  HIPC(hipMemcpyAsync(dcoef.p, cf.data(), (size_t)nf * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  auto pass = [&] {
+    cheb_diag_term(len_rows, b, nf, w.d(), t1.d(), t2.d(), x.d(), 0.5, 0.25, w.d(), dcoef.d(), dd.d(), dq.d(),
+                   false, false, ctx->stream);
+  };
+  int st = RBL_OK;
+  pass();  // warm-up
+  if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+  for (int r = 0; r < reps; ++r) pass();
+  if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+  float el = 0.f;
+  if (hipEventElapsedTime(&el, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+  *ms = (double)el / reps;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_diag_pass: a HIP call failed");
+  return RBL_OK;
+}
+
 // ---- Rayleigh-Ritz on A -------------------------------------------------------------------
 int rbl_ritz_project(rbl_ctx* ctx, int nblocks, int k, const double* S, double* H_out) {
   if (!ctx || nblocks < 1 || k < 1 || !S || !H_out)

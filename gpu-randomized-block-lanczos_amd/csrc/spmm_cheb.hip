@@ -25,6 +25,12 @@
 // of <t_j,t_j> and <t_j,t_{j-1}> — 3 reads + 1 write per element, no second sweep for the dots,
 // the sums in the fixed order of resid_partial.
 //
+// cheb_diag_term is the row pass of the diagonals of nf Chebyshev series at once (rbl_cheb_diag:
+// diag f(A) by probing): the same unscaled term, and in the same sweep the sums ALONG each row
+// over the b probe columns, s[row] = sum_c X[row][c] t_j[row][c], added into nf accumulators per
+// row with the term's coefficients — 4 reads + 1 write per element plus 16 nf / b bytes for D, one
+// recurrence for all nf functions.  sign_block turns a block into its signs (Rademacher probes).
+//
 // resid_partial forms the per-workgroup partials of the column sums of (Z - X diag(theta))^2 —
 // the true residuals ||A v - theta v||^2 of rbl_ritz_finish — summed in a fixed order (each
 // thread over its rows ascending, then the workgroup's row groups ascending in LDS; reduce_slab
@@ -256,6 +262,114 @@ void launch_cheb_moment(int grid, int64_t nrows, int cw, const double* W, const 
 #undef RBL_MOMENT_LAUNCH
 }
 
+// One term of the diagonal recurrence (rbl_cheb_diag) after its SpMM W = A t_{j-1}: the term of
+// k_cheb_moment,
+//     t_j = alpha W + beta t_{j-1} (- t_{j-2}),   stored to Tout unless LAST (Tout may be W),
+// and in the same sweep the sums ALONG each row over the b probe columns,
+//     s[row] = sum_c X[row][c] t_j[row][c],   D[row][e] += coef[e] s[row],  e < nf
+// (coef: the nf coefficients of this term; D: n x nf row-major).  FIRST (j = 1: t_{j-1} = X, T1 and
+// T2 are not read, coef holds the 2 nf coefficients of terms 0 and 1): also q[row] = sum_c X^2,
+// qout[row] = q and D[row][e] = coef[e] q + coef[nf + e] s — D is not read.
+// The thread mapping is k_cheb_moment's: a row is cw <= 256 slots of type T, the workgroup covers
+// a tile of nrg = 256 / cw whole rows (thread t reads slot t of the tile), tiles are walked
+// grid-stride.  A row never leaves its tile pass (b <= 256), so there is no cross-chunk
+// accumulation: each thread stages its slot's products in LDS, and the thread that owns (row, e)
+// adds the row's slots ascending and does the read-modify-write of D.  No atomics, one owner per
+// element of D: the same bits on every run.  The LDS stage is double-buffered, one barrier per
+// tile (a buffer is rewritten two tiles later, after the barrier of the tile between).
+template <typename T>
+__device__ __forceinline__ double slot_dot(T a, T b);
+template <>
+__device__ __forceinline__ double slot_dot<double>(double a, double b) {
+  return a * b;
+}
+template <>
+__device__ __forceinline__ double slot_dot<d2v>(d2v a, d2v b) {
+  return a.x * b.x + a.y * b.y;
+}
+
+template <typename T, bool FIRST, bool LAST>
+__global__ __launch_bounds__(kChebThreads) void k_cheb_diag(int64_t nrows, int cw, int nf, const T* W,
+                                                            const T* __restrict__ T1,
+                                                            const T* __restrict__ T2,
+                                                            const T* __restrict__ X, double alpha,
+                                                            double beta, T* Tout,
+                                                            const double* __restrict__ coef,
+                                                            double* __restrict__ D,
+                                                            double* __restrict__ qout) {
+  constexpr int NQ = FIRST ? 2 : 1;
+  __shared__ double sm[2][NQ][kChebThreads];
+  const int nrg = kChebThreads / cw;  // rows per tile (cw <= 256)
+  const int rg = threadIdx.x / cw, cl = threadIdx.x % cw;
+  const int64_t ntiles = (nrows + nrg - 1) / nrg;
+  int buf = 0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, buf ^= 1) {
+    const int64_t r0 = tile * nrg, r = r0 + rg;
+    double s = 0.0, q = 0.0;
+    if (rg < nrg && r < nrows) {
+      const int64_t i = r * cw + cl;
+      const T x = X[i];
+      T t;
+      if constexpr (FIRST) {
+        t = alpha * W[i] + beta * x;
+        q = slot_dot<T>(x, x);
+      } else {
+        t = alpha * W[i] + beta * T1[i];
+        t -= T2[i];
+      }
+      s = slot_dot<T>(x, t);
+      if constexpr (!LAST) Tout[i] = t;
+    }
+    sm[buf][0][threadIdx.x] = s;
+    if constexpr (FIRST) sm[buf][1][threadIdx.x] = q;
+    __syncthreads();
+    const int64_t left = nrows - r0;
+    const int rows = left < nrg ? (int)left : nrg;
+    for (int idx = threadIdx.x; idx < rows * nf; idx += kChebThreads) {
+      const int g = idx / nf, e = idx - g * nf;
+      const double* ps = &sm[buf][0][g * cw];
+      double rs = 0.0;
+      for (int c = 0; c < cw; ++c) rs += ps[c];
+      const int64_t di = r0 * nf + idx;  // = (r0 + g) * nf + e
+      if constexpr (FIRST) {
+        const double* pq = &sm[buf][1][g * cw];
+        double rq = 0.0;
+        for (int c = 0; c < cw; ++c) rq += pq[c];
+        D[di] = coef[e] * rq + coef[nf + e] * rs;
+        if (e == 0) qout[r0 + g] = rq;
+      } else {
+        D[di] += coef[e] * rs;
+      }
+    }
+  }
+}
+
+template <typename T>
+void launch_cheb_diag(int grid, int64_t nrows, int cw, int nf, const double* W, const double* T1,
+                      const double* T2, const double* X, double alpha, double beta, double* Tout,
+                      const double* coef, double* D, double* qout, bool first, bool last,
+                      hipStream_t s) {
+  const T *w = reinterpret_cast<const T*>(W), *t1 = reinterpret_cast<const T*>(T1),
+          *t2 = reinterpret_cast<const T*>(T2), *x = reinterpret_cast<const T*>(X);
+  T* to = reinterpret_cast<T*>(Tout);
+#define RBL_DIAG_LAUNCH(F, L)                                                                       \
+  hipLaunchKernelGGL((k_cheb_diag<T, F, L>), dim3(grid), dim3(kChebThreads), 0, s, nrows, cw, nf, w, \
+                     t1, t2, x, alpha, beta, to, coef, D, qout)
+  if (first && last) RBL_DIAG_LAUNCH(true, true);
+  else if (first) RBL_DIAG_LAUNCH(true, false);
+  else if (last) RBL_DIAG_LAUNCH(false, true);
+  else RBL_DIAG_LAUNCH(false, false);
+#undef RBL_DIAG_LAUNCH
+}
+
+// x = +1 where x >= 0 (0 and -0 included), -1 where x < 0, in place: the signs of the N(0,1) draw
+// are a Rademacher block (rbl_cheb_diag with RBL_PROBE_SIGN).
+__global__ __launch_bounds__(kChebThreads) void k_sign_block(int64_t len, double* x) {
+  const int64_t stride = (int64_t)gridDim.x * kChebThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kChebThreads + threadIdx.x; i < len; i += stride)
+    x[i] = x[i] < 0.0 ? -1.0 : 1.0;
+}
+
 __global__ __launch_bounds__(kChebThreads) void k_copy_cols(int64_t nrows, int w, const double* __restrict__ src,
                                                             int lds, int s0, double* __restrict__ dst,
                                                             int ldd, int d0) {
@@ -334,6 +448,28 @@ void cheb_moment_term(int64_t nrows, int b, const double* W, const double* T1, c
     launch_cheb_moment<d2v>(grid, nrows, b / 2, W, T1, T2, alpha, beta, Tout, part, first, last, s);
   else
     launch_cheb_moment<double>(grid, nrows, b, W, T1, T2, alpha, beta, Tout, part, first, last, s);
+}
+
+void cheb_diag_term(int64_t nrows, int b, int nf, const double* W, const double* T1, const double* T2,
+                    const double* X, double alpha, double beta, double* Tout, const double* coef,
+                    double* D, double* qout, bool first, bool last, hipStream_t s) {
+  if (nrows <= 0 || b <= 0 || b > kChebThreads || nf <= 0) return;
+  const bool vec = b % 2 == 0 && aligned16(W) && aligned16(X) && (first || (aligned16(T1) && aligned16(T2))) &&
+                   (last || aligned16(Tout));
+  const int cw = vec ? b / 2 : b;
+  const int nrg = kChebThreads / cw;
+  const int64_t ntiles = (nrows + nrg - 1) / nrg;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)cu_count() * kChebPerCu));
+  if (vec)
+    launch_cheb_diag<d2v>(grid, nrows, cw, nf, W, T1, T2, X, alpha, beta, Tout, coef, D, qout, first, last, s);
+  else
+    launch_cheb_diag<double>(grid, nrows, cw, nf, W, T1, T2, X, alpha, beta, Tout, coef, D, qout, first, last,
+                             s);
+}
+
+void sign_block(int64_t len, double* x, hipStream_t s) {
+  if (len <= 0) return;
+  hipLaunchKernelGGL(k_sign_block, dim3(stream_grid(len, kChebPerCu)), dim3(kChebThreads), 0, s, len, x);
 }
 
 int resid_grid(int64_t nrows) {

@@ -7,7 +7,10 @@ largest eigenpairs through a Chebyshev filter, ``RBL_interior(A, k, b, sigma)`` 
 nearest sigma through a Chebyshev delta series, ``RBL_interval(A, (x0, x1), b)`` all eigenpairs in
 an interval (``spectral_density`` / ``eig_count``: the Chebyshev moments behind it); each of the
 square-A drivers takes ``update=(P, S)`` for the implicit operator A + P S P^T (``rbl.lowrank``:
-``modularity_update``, ``deflation_update``, ``centering_update``, ``RBL_modularity``); ``Context`` wraps the C-ABI of
+``modularity_update``, ``deflation_update``, ``centering_update``, ``RBL_modularity``);
+``apply_function`` / ``trace_function`` / ``diag_function`` (``rbl.funm``) give f(A) B, tr f(A) and
+diag f(A) by Chebyshev series (``heat_kernel_signature``, ``subgraph_centrality``, ``local_density``,
+``logdet``); ``Context`` wraps the C-ABI of
 librbl_hip.so (include/rbl_hip.h).  Importing this package loads the HIP library and fails
 loudly if it has not been built: there is no CPU fallback.
 """
@@ -26,3 +29,5 @@ from .density import (RBL_interval, check_moments, eig_count, interval_degree, i
                       jackson, kpm_count, kpm_density, spectral_density)
 from .lowrank import (RBL_modularity, centering_update, deflation_update,  # noqa: F401
                       modularity_update)
+from .funm import (DiagResult, apply_function, cheb_coeffs, cheb_fit, diag_function, diag_series,  # noqa: F401
+                   heat_kernel_signature, local_density, logdet, subgraph_centrality, trace_function)

@@ -48,6 +48,9 @@ RBL_BUILD_VARIANTS = 1
 # a rectangular B (rbl_set_matrix_normal): what rbl_spmm_kernel_for / rbl_matrix_format report
 RBL_SPMM_KERNEL_RECT = 8
 RBL_MATRIX_FORMAT_RECT = 5
+# rbl_cheb_diag: the block drawn when X is NULL
+RBL_PROBE_GAUSS = 0
+RBL_PROBE_SIGN = 1
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -109,6 +112,9 @@ SIGNATURES = {
     "rbl_bench_series_pass": (C.c_int, [_p, _i64, C.c_int, _pd, _pd]),
     "rbl_cheb_moments": (C.c_int, [_p, C.c_int, C.c_int, C.c_double, C.c_double, _pd, _u64, _pd]),
     "rbl_bench_moment_pass": (C.c_int, [_p, _i64, C.c_int, C.c_int, _pd]),
+    "rbl_cheb_diag": (C.c_int, [_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _pd, _pd, _u64,
+                                C.c_int, _pd, _pd]),
+    "rbl_bench_diag_pass": (C.c_int, [_p, _i64, C.c_int, C.c_int, C.c_int, _pd]),
     "rbl_set_lowrank": (C.c_int, [_p, C.c_int, _pd, _pd]),
     "rbl_get_lowrank": (C.c_int, [_p, C.POINTER(C.c_int), _pd, _pd]),
     "rbl_bench_lowrank_pass": (C.c_int, [_p, _i64, C.c_int, C.c_int, C.c_int, _pd, _pd]),

@@ -242,7 +242,7 @@ class Context:
     def set_lowrank(self, P, S) -> None:
         """The operator becomes A + P S P^T (rbl_set_lowrank): P n x r, S r x r symmetric,
         1 <= r <= 32, both copied to the device; a 1-D P with a scalar S is r = 1; ``None, None``
-        clears the update.  While set, apply / start / step / the Chebyshev filters / cheb_moments /
+        clears the update.  While set, apply / start / step / the Chebyshev filters / cheb_moments / cheb_diag /
         ritz_project run on the updated operator.  Square A, one rank, fp64 basis."""
         if P is None and S is None:
             self._check(lib.rbl_set_lowrank(self._h, 0, None, None), "rbl_set_lowrank")
@@ -476,6 +476,40 @@ class Context:
         self._check(lib.rbl_cheb_moments(self._h, b, degree, float(lo), float(hi), xp, int(seed) & (2**64 - 1),
                                          dptr(mom)), "rbl_cheb_moments")
         return mom
+
+    def cheb_diag(self, b: int, lo: float, hi: float, coef, X=None, seed: int = 0, probe="sign"):
+        """rbl_cheb_diag: (num, den) with num[row, e] = sum_c x_c[row] (p_e(A) x_c)[row] and
+        den[row] = sum_c x_c[row]^2 over a block of b vectors, p_e = sum_j coef[j, e] T_j((A - cI)/e),
+        from ONE recurrence of degree = coef.shape[0] - 1 >= 1 SpMMs for all nf = coef.shape[1] <= 32
+        series (a 1-D coef is one series); num / den[:, None] estimates the diagonals.  [lo, hi]
+        must enclose the whole spectrum.  X: n x b host block (b <= 256), or None for the device's
+        draw from `seed`: probe "sign" (+-1) or "gauss" (N(0,1)).  rbl.funm builds on it."""
+        b = int(b)
+        coef = np.asarray(coef, dtype=np.float64)
+        if coef.ndim == 1:
+            coef = coef[:, None]
+        if coef.ndim != 2:
+            raise ValueError("cheb_diag: coef must be (degree + 1) x nf")
+        coef = np.asfortranarray(coef)
+        degree, nf = coef.shape[0] - 1, coef.shape[1]
+        if isinstance(probe, str):
+            try:
+                probe = {"gauss": _lib.RBL_PROBE_GAUSS, "sign": _lib.RBL_PROBE_SIGN}[probe]
+            except KeyError:
+                raise ValueError('cheb_diag: probe must be "sign" or "gauss"') from None
+        n, r0, r1, _ = self.matrix_info()
+        xp = None
+        if X is not None:
+            X = np.asfortranarray(X, dtype=np.float64)
+            if X.ndim != 2 or X.shape != (r1 - r0, b):
+                raise ValueError(f"cheb_diag: X must be {r1 - r0} x {b}")
+            xp = dptr(X)
+        num = np.zeros((max(r1 - r0, 1), max(nf, 1)), order="F")
+        den = np.zeros(max(r1 - r0, 1))
+        self._check(lib.rbl_cheb_diag(self._h, b, degree, float(lo), float(hi), nf, dptr(coef), xp,
+                                      int(seed) & (2**64 - 1), int(probe), dptr(num), dptr(den)),
+                    "rbl_cheb_diag")
+        return num[: r1 - r0], den[: r1 - r0]
 
     def ritz_project(self, nblocks: int, k: int, S: np.ndarray) -> np.ndarray:
         """rbl_ritz_project: V = [Q_1..Q_nblocks] S and W = A V stay on the device; returns

@@ -427,6 +427,41 @@ int rbl_cheb_moments(rbl_ctx* ctx, int b, int degree, double lo, double hi, cons
  * row pass of a middle term with its partial-sum reduction, over blocks of len_rows x b doubles
  * allocated for the call. */
 int rbl_bench_moment_pass(rbl_ctx* ctx, int64_t len_rows, int b, int reps, double* ms);
+/* rbl_cheb_diag: the diagonals of nf matrix functions at once (subgraph centrality diag exp(A),
+ * heat-kernel signatures diag exp(-t L) at many t, the local density of states at many energies;
+ * rbl.funm), by the probing estimator over a block of b vectors x_c:
+ *     num_out[row + n_local e] = sum_c x_c[row] (p_e(A) x_c)[row],   den_out[row] = sum_c x_c[row]^2,
+ *     p_e(A) = sum_{j=0..degree} coef[j + (degree + 1) e] T_j((A - cI) / e'),  e < nf,
+ * c = (lo + hi) / 2, e' = (hi - lo) / 2, with [lo, hi] enclosing the WHOLE spectrum of A; num / den
+ * estimates diag p_e(A) (exactly, when the x_c are identity columns).  coef: host, (degree + 1) x nf
+ * column-major (function e's coefficients contiguous); it is copied.  X: host n_local x b
+ * column-major, or NULL for a block drawn on the device from `seed`: probe = RBL_PROBE_GAUSS the
+ * counter-based N(0,1) draw of rbl_start, RBL_PROBE_SIGN its signs (+-1, 0 -> +1: Rademacher, den =
+ * b exactly).  probe is checked but not used when X is given.  num_out: host, n_local x nf
+ * column-major, rows in the order rbl_apply returns them; den_out: host, n_local.
+ * ONE recurrence serves all nf functions: `degree` SpMMs (the operator routine of every other entry
+ * point, so a low-rank update that is set applies) and after each ONE row pass that forms t_j,
+ * s[row] = sum_c X[row][c] t_j[row][c] and D[row][e] += coef[j][e] s[row] — 40 + 16 nf / b bytes per
+ * element and term, against 48 for every function through rbl_apply_filter.  The row sums run in a
+ * fixed order with no atomics (each thread its slot's columns, the row's slots ascending through
+ * LDS, one owner thread per element of D): two calls give the same bits.  The call allocates its
+ * own four work blocks (X is kept beside the three of the recurrence), D and the device copy of
+ * coef: the Krylov basis, a run in progress and a filter or series that is set are untouched.
+ * Timed under "AQ".
+ * b <= 256: a row of the block is then at most 256 slots of the row pass, which finishes it inside
+ * one tile pass of a workgroup; no cross-chunk row accumulation exists.
+ * Limits (RBL_ERR_INVALID, before any allocation; the context stays usable): 1 <= b <= 256;
+ * 1 <= degree <= 65535; 1 <= nf <= 32; lo < hi, both finite; coef non-NULL, every entry finite;
+ * probe RBL_PROBE_GAUSS or RBL_PROBE_SIGN; num_out and den_out non-NULL; one rank only; no
+ * rectangular B.  RBL_ERR_STATE without a matrix. */
+#define RBL_PROBE_GAUSS 0   /* the N(0,1) draw of rbl_start */
+#define RBL_PROBE_SIGN  1   /* its signs: Rademacher */
+int rbl_cheb_diag(rbl_ctx* ctx, int b, int degree, double lo, double hi, int nf, const double* coef,
+                  const double* X, uint64_t seed, int probe, double* num_out, double* den_out);
+/* Diagnostics: the time per pass (ms, hipEvents, mean over `reps` after one warm-up) of the
+ * diagonal row pass of a middle term, over blocks of len_rows x b doubles and a len_rows x nf D
+ * allocated for the call.  1 <= b <= 256, 1 <= nf <= 32. */
+int rbl_bench_diag_pass(rbl_ctx* ctx, int64_t len_rows, int b, int nf, int reps, double* ms);
 
 /* ---- implicit symmetric low-rank update: the operator A + P S P^T ----------------------------
  * (No reference equivalent.)  rbl_set_lowrank: with P (n x r, host, column-major) and S (r x r,
@@ -436,7 +471,7 @@ int rbl_bench_moment_pass(rbl_ctx* ctx, int64_t len_rows, int b, int reps, doubl
  * eigenpairs already found, a double-centred kernel matrix H K H (r = 2, S not diagonal) — which
  * is dense and never formed.  All of them go through one operator routine, so rbl_apply,
  * rbl_start, rbl_step, rbl_step_async, the restarted entry points, both Chebyshev filters
- * (rbl_apply_filter: p(Op)), rbl_cheb_moments and rbl_ritz_project / rbl_ritz_finish (W = Op V,
+ * (rbl_apply_filter: p(Op)), rbl_cheb_moments, rbl_cheb_diag and rbl_ritz_project / rbl_ritz_finish (W = Op V,
  * residuals ||Op v - theta v||) all see Op.  After the SpMM and its fused 3-term epilogue three
  * passes run in stream order, with no host round trip:
  *     w = P^T X (r x b),   c = S w,   U[row, :] += P[row, :] c   (rows < n_local)

@@ -660,3 +660,35 @@ function RBL_gpu_eigcount(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, x0
         ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
     end
 end
+
+# The diagonals of nf Chebyshev series of A at once (no reference equivalent): with coef
+# ((degree + 1) x nf, column e the coefficients of p_e = sum_j coef[j+1, e] T_j((A - cI)/e) on
+# [lo, hi], which must enclose the whole spectrum) over a block of b <= 256 device-drawn probe
+# vectors x_c, one rbl_cheb_diag call returns
+#   num[row, e] = sum_c x_c[row] (p_e(A) x_c)[row]   and   den[row] = sum_c x_c[row]^2,
+# so num ./ den estimates diag p_e(A) (Bekas, Kokiopoulou and Saad) — subgraph centrality, heat-kernel
+# signatures at many times, the local density of states at many energies — from ONE recurrence of
+# `degree` SpMMs for all nf <= 32 functions.  probe = 1: Rademacher (the signs of the N(0,1) draw,
+# den = b exactly), 0: N(0,1).  The same call as rbl/rbl_gpu.py Context.cheb_diag with X = None.
+# Returns (num, den).  One GPU.
+function RBL_gpu_diagfun(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, coef::Matrix{Float64},
+                         lo::Float64, hi::Float64, b::Int64;
+                         seed::UInt64 = rand(UInt64), probe::Int64 = 1, device::Int = 0)
+    n = size(A, 2)
+    degree, nf = size(coef, 1) - 1, size(coef, 2)
+    ctx = rbl_context(device)
+    try
+        set_matrix!(ctx, A)
+        num = zeros(Float64, n, nf)
+        den = zeros(Float64, n)
+        rbl_check(ctx, ccall((:rbl_cheb_diag, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cint, Cdouble, Cdouble, Cint, Ptr{Float64}, Ptr{Float64},
+                              UInt64, Cint, Ptr{Float64}, Ptr{Float64}),
+                             ctx, Cint(b), Cint(degree), lo, hi, Cint(nf), coef, C_NULL, seed, Cint(probe),
+                             num, den),
+                  "rbl_cheb_diag")
+        return num, den
+    finally
+        ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
+    end
+end
