@@ -5,6 +5,10 @@
 // (nearly) rank deficient — Krylov exhaustion in the reference's own tests —
 // shifted CholQR3 (Fukaya et al. 2020: shift s = 11 (n b + b (b+1)) u ||U||^2, then two
 // unshifted passes).  R has a non-negative diagonal.
+// An exactly zero column of the block (g_jj = 0) is deflated in every kernel below: pivot 1,
+// R(j, j) = 0, its Q column stays zero.  Its zero pivot used to fail and shift each of the three
+// passes, the last one included, which left the OTHER columns orthonormal only to the shift
+// (1e-10 .. 1e-9 at n = 1040, b = 8 .. 32) instead of to rounding.
 #include <cstdlib>
 
 #include "kernels.hpp"
@@ -64,7 +68,9 @@ __global__ __launch_bounds__(256) void k_chol(const double* __restrict__ G, int 
       __syncthreads();
       for (int j = 0; j < b; ++j) {
         if (tid == 0) {
-          const double d = M(j, j);
+          // an exactly zero column of U (g_jj = 0, hence a zero row and column of G): pivot 1,
+          // so that it neither fails nor shifts the other columns; its R(j, j) is set to 0 below
+          const double d = gd[j] == 0.0 ? 1.0 : M(j, j);
           const double gjj = gd[j] + sh;
           if (!(d > 0.0) || !isfinite(d)) {
             fail = 1;
@@ -108,6 +114,11 @@ __global__ __launch_bounds__(256) void k_chol(const double* __restrict__ G, int 
       }
     }
   }
+  __syncthreads();
+  // R(j, j) = 0 for an exactly zero column, in R and in the Rtot product (R^-1 (j, j) stays 1:
+  // it multiplies the zero column)
+  for (int j = tid; j < b; j += nt)
+    if (G[j * b + j] == 0.0) M(j, j) = 0.0;
   __syncthreads();
   for (int e = tid; e < b * b; e += nt) {
     const int r = e / b, c = e % b;
@@ -175,8 +186,10 @@ __global__ __launch_bounds__(64) void k_chol_reg(const double* __restrict__ G, i
       fail = 0;
 #pragma unroll
       for (int j = 0; j < B; ++j) {
-        const double d = bcast(m[j], j);  // M(j, j), held by lane j
-        const double gjj = G[j * B + j] + sh;
+        const double g0 = G[j * B + j];
+        const double dj = bcast(m[j], j);     // M(j, j), held by lane j
+        const double d = g0 == 0.0 ? 1.0 : dj;  // an exactly zero column: pivot 1 (see k_chol)
+        const double gjj = g0 + sh;
         if (!(d > 0.0) || !isfinite(d)) {
           fail = 1;
         } else if (attempt == 0 && mode == 0 && d < 1e-15 * gjj) {
@@ -212,6 +225,12 @@ __global__ __launch_bounds__(64) void k_chol_reg(const double* __restrict__ G, i
       for (int k = i + 1; k < B; ++k) acc += bcast(m[i], k) * x[k];  // x[k] = 0 for k > c
       if (i < c) x[i] = -acc / mii;
     }
+  }
+  {  // R(j, j) = 0 for an exactly zero column, in R and in the Rtot product (see k_chol)
+    const bool deadc = G[cc * B + cc] == 0.0;
+#pragma unroll
+    for (int r = 0; r < B; ++r)
+      if (r == c && deadc) m[r] = 0.0;
   }
   if (c < B) {
 #pragma unroll
@@ -287,8 +306,10 @@ __global__ __launch_bounds__(64) void k_chol_elim(const double* __restrict__ G, 
       fail = 0;
 #pragma unroll
       for (int j = 0; j < B; ++j) {
-        const double d = bcast(m[j], j);  // M(j, j), held by lane j
-        const double gjj = G[j * B + j] + sh;
+        const double g0 = G[j * B + j];
+        const double dj = bcast(m[j], j);     // M(j, j), held by lane j
+        const double d = g0 == 0.0 ? 1.0 : dj;  // an exactly zero column: pivot 1 (see k_chol)
+        const double gjj = g0 + sh;
         if (!(d > 0.0) || !isfinite(d)) {
           fail = 1;
         } else if (attempt == 0 && mode == 0 && d < 1e-15 * gjj) {
@@ -316,6 +337,12 @@ __global__ __launch_bounds__(64) void k_chol_elim(const double* __restrict__ G, 
   }
   const bool bad = !zero && fail;
   const bool ok = !zero && !bad;
+  {  // R(j, j) = 0 for an exactly zero column, in R and in the Rtot product (see k_chol)
+    const bool deadc = G[cc * B + cc] == 0.0;
+#pragma unroll
+    for (int r = 0; r < B; ++r)
+      if (r == c && deadc) m[r] = 0.0;
+  }
   if (c < B) {
 #pragma unroll
     for (int r = 0; r < B; ++r) {
@@ -394,8 +421,10 @@ __global__ __launch_bounds__(64) void k_chol_elim2(const double* __restrict__ G,
       fail = 0;
 #pragma unroll
       for (int j = 0; j < B; ++j) {
-        const double d = bcast(v[j], j);  // M(j, j), held by lane j
-        const double gjj = G[j * B + j] + sh;
+        const double g0 = G[j * B + j];
+        const double dj = bcast(v[j], j);     // M(j, j), held by lane j
+        const double d = g0 == 0.0 ? 1.0 : dj;  // an exactly zero column: pivot 1 (see k_chol)
+        const double gjj = g0 + sh;
         if (!(d > 0.0) || !isfinite(d)) {
           fail = 1;
         } else if (attempt == 0 && mode == 0 && d < 1e-15 * gjj) {
@@ -425,6 +454,12 @@ __global__ __launch_bounds__(64) void k_chol_elim2(const double* __restrict__ G,
   }
   const bool bad = !zero && fail;
   const bool ok = !zero && !bad;
+  {  // R(j, j) = 0 for an exactly zero column, in R and in the Rtot product (see k_chol)
+    const bool deadc = !isx && G[col * B + col] == 0.0;
+#pragma unroll
+    for (int r = 0; r < B; ++r)
+      if (r == col && deadc) v[r] = 0.0;
+  }
   if (live) {
 #pragma unroll
     for (int r = 0; r < B; ++r) {
