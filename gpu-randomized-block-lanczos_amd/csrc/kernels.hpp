@@ -392,6 +392,21 @@ void tsmm(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Pane
           double alpha, double beta, const int* skip, hipStream_t s, double* xslab = nullptr,
           int* xgrid = nullptr);
 
+// --- compress.hip: in-place basis compression (rbl_thick_restart) --------------------------
+// Panels 0 .. p / X.w - 1 of the run X (m = X.count panels) <- [X_0 .. X_{m-1}] S_dev, with S_dev
+// (m X.w) x p row-major on the device, p a multiple of X.w, X.w <= p <= kCompressMaxCols and
+// p / X.w <= m.  In place: a workgroup owns whole rows and finishes every load of them before its
+// first store (a workgroup barrier between), so no scratch of size n is needed.  X.w in {16, 32}
+// runs on fp64 MFMA with the accumulators of all p columns of a 64-row tile in registers (each
+// basis element read from HBM once); any other width, or `generic`, takes one thread per output
+// column.  Ascending-k sums, no atomics: the same bits on every call.  false: shape not served
+// (nothing launched).  kCompressMaxCols is RBL_COMPRESS_MAX_COLS: 64 rows x 512 columns are 128
+// fp64 accumulators per lane, half the 512 registers of a lane at one wave per SIMD.
+constexpr int kCompressMaxCols = 512;
+bool basis_compress_fast(const PanelRun& X, int p);
+bool basis_compress(int64_t nrows, const PanelRun& X, const double* S_dev, int p, hipStream_t s,
+                    bool generic = false);
+
 // --- reorth.hip: v_mfma_f64_4x4x4f64 fast paths (panel widths 16 / 32), selected by
 // gram_splits / gram_partial / tsmm above when applicable.
 bool gram44_ok(int64_t nrows, int nW, int w, int xcount, int xw);

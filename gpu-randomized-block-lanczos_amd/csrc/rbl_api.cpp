@@ -228,6 +228,14 @@ struct rbl_ctx {
   // vector j at d_lock + j * nloc (a width-1 panel)
   double* d_lock = nullptr;
   int nlock = 0, lock_cap = 0;
+  // thick restart (rbl_thick_restart): arrow_kb > 0 while the arrow step is pending — the basis is
+  // [Y_1 .. Y_kb, Q_{m+1}] and step kb + 1 forms U = Op Q_{m+1} - [Y_1 .. Y_kb] W^T with W^T
+  // ((kb b) x b row-major) in d_arrow_W; d_tr_S holds the compression's S ((m b) x (kb b)
+  // row-major).  Both grow on demand and hold nothing of size n.
+  int arrow_kb = 0;
+  double* d_arrow_W = nullptr;
+  double* d_tr_S = nullptr;
+  size_t arrow_W_cap = 0, tr_S_cap = 0;
   // Chebyshev filter (rbl_set_filter; degree 0: none): the Krylov operator is p(A), applied by a
   // three-term recurrence through two work blocks beside U, each (n_local + kRowPad) x filt_cols
   // and zeroed like every block an SpMM writes; sized at rbl_start
@@ -2393,6 +2401,10 @@ void free_run(rbl_ctx* ctx) {
   hipFree(ctx->d_flags); ctx->d_flags = nullptr;
   hipFree(ctx->d_lock); ctx->d_lock = nullptr;
   ctx->nlock = ctx->lock_cap = 0;
+  hipFree(ctx->d_arrow_W); ctx->d_arrow_W = nullptr;
+  hipFree(ctx->d_tr_S); ctx->d_tr_S = nullptr;
+  ctx->arrow_W_cap = ctx->tr_S_cap = 0;
+  ctx->arrow_kb = 0;
   hipFree(ctx->d_filt[0]); hipFree(ctx->d_filt[1]); hipFree(ctx->d_filt[2]);
   ctx->d_filt[0] = ctx->d_filt[1] = ctx->d_filt[2] = nullptr;
   ctx->filt_cols = 0;
@@ -2459,6 +2471,7 @@ void free_matrix(rbl_ctx* ctx) {
   hipFree(ctx->d_rect_y); ctx->d_rect_y = nullptr; ctx->rect_y_cols = 0;
   free_rect_shift(ctx);
   free_lowrank(ctx);
+  ctx->arrow_kb = 0;  // a pending arrow step belongs to the operator its basis was built with
   ctx->rect = false;
   ctx->rect_m = 0;
   hipFree(ctx->d_dense); ctx->d_dense = nullptr;
@@ -3479,6 +3492,7 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   }
   const bool reuse = same_shape && cur_slots == dev_slots;
   ctx->nlock = 0;  // a new problem: no locked vectors
+  ctx->arrow_kb = 0;
   ctx->cloc_step = 0;
   ctx->step_flags.clear();
   // the allocations below fail alone on one rank (its HBM): every rank then learns of it before
@@ -3786,8 +3800,23 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
   // (fp64 basis, band tiles at b = 32; no collective depends on the choice)
   // (not with a Chebyshev filter: the staging fusion assumes U = A Q_i from one SpMM)
   const bool filt = has_filter(ctx);
+  // the arrow step after a thick restart (rbl_thick_restart): Q_i = Q_{m+1} couples to every kept
+  // block, U = Op Q_i - [Y_1 .. Y_kb] W^T; the operator runs without the 3-term epilogue, the local
+  // reorth on its own pass (the staging fusion assumes the plain 3-term shape) and A_i comes from
+  // the Gram of the final U
+  const bool arrow = ctx->arrow_kb > 0 && i == ctx->arrow_kb + 1;
+  if (arrow && (f32 || spilled(ctx) || ctx->nranks > 1))
+    return fail(ctx, RBL_ERR_STATE, "rbl_step: the arrow step needs one rank and an HBM-resident fp64 basis");
+  auto arrow_update = [&]() -> int {  // U -= [Y_1 .. Y_kb] W^T, one tsmm over the kept run
+    PanelRun Y;
+    Y.base = slotp(ctx, 0);
+    Y.stride = ctx->slot;
+    Y.count = ctx->arrow_kb;
+    Y.w = b;
+    return tsmm_checked(ctx, Y, ctx->d_arrow_W, b, pan1(ctx->d_U, b), -1.0, 1.0, nullptr);
+  };
   const bool lfuse = !f32 && i >= 2 && (ctx->fuse & 4) && fused && !ctx->dense && ctx->nloc > 0 &&
-                     !filt && rbl_spmm_kernel_for(ctx, b) == 5 && spmm_bt_locfix_ok(csr(ctx), b);
+                     !filt && !arrow && rbl_spmm_kernel_for(ctx, b) == 5 && spmm_bt_locfix_ok(csr(ctx), b);
   const double* Cloc = nullptr;
   int64_t lf_lo = 0, lf_hi = ctx->nloc;
   if (!f32 && i >= 2) {
@@ -3831,7 +3860,9 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
     CHK(ensure_filter_bufs(ctx, b));
     StageScope t(ctx, RBL_STAGE_AQ);
     CHK(filter_apply(ctx, Qi, b, ctx->d_U, ctx->d_filt));
-    if (i >= 2) {
+    if (arrow) {
+      CHK(arrow_update());
+    } else if (i >= 2) {
       transpose_small(smallp(ctx, S_BPREV), smallp(ctx, S_BT), b, ctx->stream);
       CHK(tsmm_checked(ctx, run1(Qm, b), smallp(ctx, S_BT), b, pan1(ctx->d_U, b), -1.0, 1.0, nullptr));
     }
@@ -3892,8 +3923,13 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
                    ctx->d_slab, &ai_parts, Qin32, Qm32))
         return fail(ctx, RBL_ERR_INVALID, "internal: fp32 band-tile SpMM not applicable");
     } else {
-      ai_parts = apply_A(ctx, Qin, off, b, ctx->d_U, Qm, i >= 2 ? smallp(ctx, S_BPREV) : nullptr,
-                         ctx->d_slab, split ? Qi : nullptr, Cloc, Qi, lf_lo, lf_hi, halo_ev);
+      ai_parts = apply_A(ctx, Qin, off, b, ctx->d_U, arrow ? nullptr : Qm,
+                         i >= 2 && !arrow ? smallp(ctx, S_BPREV) : nullptr, arrow ? nullptr : ctx->d_slab,
+                         split ? Qi : nullptr, Cloc, Qi, lf_lo, lf_hi, halo_ev);
+      if (arrow && ai_parts >= 0) {
+        ai_parts = 0;
+        CHK(arrow_update());
+      }
     }
     if (ai_parts < 0) return ai_parts;
     HIPC(hipGetLastError());
@@ -3901,6 +3937,7 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
     // also where the SpMM never waited for it (a rank without rows returns from apply_A early)
     if (halo_ev) HIPC(hipStreamWaitEvent(ctx->stream, halo_ev, 0));
   }
+  if (arrow) ctx->arrow_kb = 0;
   // the push/pull split: the received partials into U (A_i is formed after this, from all of U)
   if (pushed) {
     HIPC(hipStreamWaitEvent(ctx->stream, ctx->ev_push_done, 0));
@@ -4893,6 +4930,7 @@ int rbl_num_blocks(rbl_ctx* ctx) { return ctx ? ctx->nblocks : 0; }
 // ---- restarted variants (restarted.jl) -------------------------------------------------
 int rbl_restart(rbl_ctx* ctx, int nblocks, const double* S) {
   if (ctx) ctx->cloc_step = 0;  // the basis changes outside the step
+  if (ctx) ctx->arrow_kb = 0;
   if (!ctx || !S || nblocks < 1 || nblocks > ctx->nblocks)
     return fail(ctx, RBL_ERR_INVALID, "rbl_restart: bad arguments");
   if (!ctx->d_basis) return fail(ctx, RBL_ERR_STATE, "rbl_restart: needs an fp64 run (rbl_start)");
@@ -4906,6 +4944,137 @@ int rbl_restart(rbl_ctx* ctx, int nblocks, const double* S) {
   HIPC(hipStreamSynchronize(ctx->stream));
   ctx->nblocks = 1;
   ctx->fetched = 1;
+  return RBL_OK;
+}
+
+// ---- thick restart ---------------------------------------------------------------------
+// Every refusal comes before any change: the basis, the block count and a pending arrow stay as
+// they were.
+int rbl_thick_restart(rbl_ctx* ctx, int nblocks, int keep_blocks, const double* S, const double* W) {
+  if (!ctx) return RBL_ERR_INVALID;
+  const int m = nblocks, kb = keep_blocks;
+  if (!S || !W) return fail(ctx, RBL_ERR_INVALID, "rbl_thick_restart: S or W is NULL");
+  if (ctx->nranks > 1)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_thick_restart: one rank only (nranks > 1 is not supported)");
+  if (ctx->d_basis32)
+    return fail(ctx, RBL_ERR_STATE, "rbl_thick_restart: the fp64 basis only (the current run has basis_bits = 32)");
+  if (!ctx->d_basis || ctx->nblocks < 1)
+    return fail(ctx, RBL_ERR_STATE, "rbl_thick_restart: needs an fp64 run (rbl_start)");
+  if (spilled(ctx)) return fail(ctx, RBL_ERR_STATE, "rbl_thick_restart: needs an HBM-resident basis");
+  if (ctx->fetched < ctx->nblocks)
+    return fail(ctx, RBL_ERR_STATE, "rbl_thick_restart: rbl_fetch the asynchronous steps first");
+  if (m < 1 || m + 1 != ctx->nblocks)
+    return fail(ctx, RBL_ERR_STATE, "rbl_thick_restart: nblocks + 1 must equal the current block count (" +
+                                        std::to_string(ctx->nblocks) + ")");
+  if (kb < 1 || kb >= m)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_thick_restart: keep_blocks must be in [1, nblocks)");
+  const int b = ctx->b;
+  const int64_t p = (int64_t)kb * b, mb = (int64_t)m * b;
+  if (p > RBL_COMPRESS_MAX_COLS)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_thick_restart: keep_blocks * b = " + std::to_string(p) +
+                                          " exceeds RBL_COMPRESS_MAX_COLS = " +
+                                          std::to_string(RBL_COMPRESS_MAX_COLS));
+  for (int64_t e = 0; e < mb * p; ++e)
+    if (!std::isfinite(S[e])) return fail(ctx, RBL_ERR_INVALID, "rbl_thick_restart: S has a non-finite entry");
+  for (int64_t e = 0; e < (int64_t)b * p; ++e)
+    if (!std::isfinite(W[e])) return fail(ctx, RBL_ERR_INVALID, "rbl_thick_restart: W has a non-finite entry");
+  HIPC(hipSetDevice(ctx->device));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  // S column-major (m b) x p -> row-major; W column-major b x p is W^T row-major p x b as it lies
+  std::vector<double> Sr((size_t)(mb * p));
+  for (int64_t c = 0; c < p; ++c)
+    for (int64_t r = 0; r < mb; ++r) Sr[(size_t)(r * p + c)] = S[r + c * mb];
+  if (ctx->tr_S_cap < Sr.size()) {
+    hipFree(ctx->d_tr_S);
+    ctx->d_tr_S = nullptr;
+    ctx->tr_S_cap = 0;
+    HIPC(hipMalloc(&ctx->d_tr_S, Sr.size() * sizeof(double)));
+    ctx->tr_S_cap = Sr.size();
+  }
+  if (ctx->arrow_W_cap < (size_t)(p * b)) {
+    hipFree(ctx->d_arrow_W);
+    ctx->d_arrow_W = nullptr;
+    ctx->arrow_W_cap = 0;
+    HIPC(hipMalloc(&ctx->d_arrow_W, (size_t)(p * b) * sizeof(double)));
+    ctx->arrow_W_cap = (size_t)(p * b);
+  }
+  HIPC(hipMemcpy(ctx->d_tr_S, Sr.data(), Sr.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->d_arrow_W, W, (size_t)(p * b) * sizeof(double), hipMemcpyHostToDevice));
+  {
+    StageScope t(ctx, RBL_STAGE_RITZ);
+    PanelRun X;
+    X.base = slotp(ctx, 0);
+    X.stride = ctx->slot;
+    X.count = m;
+    X.w = b;
+    if (!basis_compress(ctx->nloc, X, ctx->d_tr_S, (int)p, ctx->stream))
+      return fail(ctx, RBL_ERR_INVALID, "internal: basis_compress does not serve this shape");
+    HIPC(hipGetLastError());
+    // slot kb <- Q_{m+1} (kb < m: the compression has read slot kb and never touches slot m)
+    HIPC(hipMemcpyAsync(slotp(ctx, kb), slotp(ctx, m), ctx->slot * sizeof(double),
+                        hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  HIPC(hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  harvest_timers(ctx);
+  ctx->cloc_step = 0;  // the basis changes outside the step
+  ctx->cloc_final = false;
+  ctx->nblocks = kb + 1;
+  ctx->fetched = kb + 1;
+  ctx->arrow_kb = kb;
+  return RBL_OK;
+}
+
+// Diagnostics: hipEvent time per pass of the in-place compression of a run of m synthetic
+// rows x b blocks to keep_blocks blocks, and of the route without it — ceil(p / 64) out-of-place
+// tsmm launches, each re-reading the whole run, into a rows x 64 scratch block.  The blocks, S and
+// the scratch are allocated and zeroed for the call.
+int rbl_bench_compress_pass(rbl_ctx* ctx, int64_t rows, int b, int m, int keep_blocks, int reps,
+                            double* inplace_ms, double* sliced_ms) {
+  if (!ctx || rows < 1 || b < 1 || b > RBL_MAX_BLOCK || m < 2 || keep_blocks < 1 || keep_blocks >= m ||
+      (int64_t)keep_blocks * b > RBL_COMPRESS_MAX_COLS || reps < 1 || !inplace_ms || !sliced_ms)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_compress_pass: bad arguments");
+  HIPC(hipSetDevice(ctx->device));
+  const int p = keep_blocks * b;
+  const int64_t slot = rows * b;
+  DevBuf x, s, y;
+  const std::pair<DevBuf*, size_t> bufs[] = {{&x, (size_t)slot * m},
+                                             {&s, (size_t)m * b * p},
+                                             {&y, (size_t)rows * 64}};
+  for (const auto& q : bufs) {
+    HIPC(hipMalloc(&q.first->p, q.second * sizeof(double)));
+    HIPC(hipMemsetAsync(q.first->p, 0, q.second * sizeof(double), ctx->stream));
+  }
+  PanelRun X;
+  X.base = x.d();
+  X.stride = slot;
+  X.count = m;
+  X.w = b;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  int st = RBL_OK;
+  auto inplace = [&] {
+    if (!basis_compress(rows, X, s.d(), p, ctx->stream)) st = RBL_ERR_INVALID;
+  };
+  auto sliced = [&] {
+    for (int c0 = 0; c0 < p; c0 += 64)
+      tsmm(rows, X, s.d() + c0, p, pan1(y.d(), std::min(64, p - c0)), 1.0, 0.0, nullptr, ctx->stream);
+  };
+  auto timed = [&](auto&& fn, double* out) {
+    fn();  // warm-up
+    if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+    for (int q = 0; q < reps; ++q) fn();
+    if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+    *out = (double)ms / reps;
+  };
+  timed(inplace, inplace_ms);
+  timed(sliced, sliced_ms);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_compress_pass: a HIP call failed");
   return RBL_OK;
 }
 

@@ -1,6 +1,8 @@
 """rbl — MI355X-native Randomized Block Lanczos inner loop (host side).
 
-``RBL_gpu(A, k, b)`` mirrors Julia/RBL_gpu.jl:205, ``RBL_svd(B, k, b)`` the truncated SVD of
+``RBL_gpu(A, k, b)`` mirrors Julia/RBL_gpu.jl:205, ``RBL_thick(A, k, b, max_blocks=m)`` the same
+eigenpairs by thick-restart block Lanczos in a basis bounded by m + 1 blocks (``lanczos_thick`` on a
+loaded context; ``RBL_svd(..., max_blocks=m)`` for singular triplets), ``RBL_svd(B, k, b)`` the truncated SVD of
 images.jl:20-33 on the implicit B^T B (``shift=(u, v)``: of B - u v^T), ``RBL_pca(B, k, b)`` PCA of a
 sparse B with implicit centring on top of it, ``RBL_filtered(A, k, b, which="SA"|"LA")`` the smallest or
 largest eigenpairs through a Chebyshev filter, ``RBL_interior(A, k, b, sigma)`` the eigenpairs
@@ -21,6 +23,7 @@ from .restarted import RBL_gpu_restarted, RBL_restarted  # noqa: F401
 from .rbl_gpu import (KRYL_SZ_GPU, RESIDUAL_TOL, Context, RBL_gpu, RBLInfo, LocalGroup,  # noqa: F401
                       lanczos, rccl_version)
 from .svd import RBL_svd  # noqa: F401
+from .thick import RBL_thick, lanczos_thick, projected_matrix  # noqa: F401
 from .pca import PCAResult, RBL_pca, column_stats  # noqa: F401
 from .filtered import RBL_filtered, cheb_scalars, filter_bounds, lanczos_filtered  # noqa: F401
 from .interior import (RBL_interior, delta_coeffs, estimate_spectrum, lanczos_interior,  # noqa: F401

@@ -51,6 +51,8 @@ RBL_MATRIX_FORMAT_RECT = 5
 # rbl_cheb_diag: the block drawn when X is NULL
 RBL_PROBE_GAUSS = 0
 RBL_PROBE_SIGN = 1
+# rbl_thick_restart: the most columns keep_blocks * b the in-place compression keeps
+RBL_COMPRESS_MAX_COLS = 512
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -126,6 +128,8 @@ SIGNATURES = {
     "rbl_num_locked": (C.c_int, [_p]),
     "rbl_get_locked": (C.c_int, [_p, _pd]),
     "rbl_reorth_last": (C.c_int, [_p, C.c_int, C.c_int]),
+    "rbl_thick_restart": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd]),
+    "rbl_bench_compress_pass": (C.c_int, [_p, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _pd, _pd]),
     "rbl_num_stages": (C.c_int, []),
     "rbl_stage_name": (C.c_char_p, [C.c_int]),
     "rbl_timers": (C.c_int, [_p, _pd, C.c_int]),

@@ -420,6 +420,32 @@ class Context:
     def reorth_last(self, nblocks: int, flags: int) -> None:
         self._check(lib.rbl_reorth_last(self._h, nblocks, flags), "rbl_reorth_last")
 
+    # ---- thick restart (rbl.thick) ----
+    def thick_restart(self, nblocks: int, S: np.ndarray, W: np.ndarray) -> None:
+        """rbl_thick_restart after m = nblocks steps: the basis [Q_1 .. Q_m, Q_{m+1}] becomes
+        [Q S, Q_{m+1}] in place.  S: (m b) x (kb b) chosen eigenvector columns of the projected
+        matrix, W: b x (kb b) = B_{m+1} S[last b rows]; kb < m blocks are kept.  The next step is
+        kb + 1, the arrow step U = Op Q_{m+1} - (Q S) W^T."""
+        b = self.b
+        S = np.asfortranarray(S, dtype=np.float64)
+        W = np.asfortranarray(W, dtype=np.float64)
+        if S.ndim != 2 or S.shape[0] != nblocks * b or S.shape[1] < b or S.shape[1] % b:
+            raise ValueError(f"thick_restart: S must be {nblocks * b} x (keep_blocks * {b})")
+        if W.shape != (b, S.shape[1]):
+            raise ValueError(f"thick_restart: W must be {b} x {S.shape[1]}")
+        self._check(lib.rbl_thick_restart(self._h, int(nblocks), S.shape[1] // b, dptr(S), dptr(W)),
+                    "rbl_thick_restart")
+
+    def bench_compress_pass(self, rows: int, b: int, m: int, keep_blocks: int, reps: int = 5):
+        """(inplace_ms, sliced_ms) per pass of the in-place compression of m synthetic rows x b
+        blocks to keep_blocks, and of the ceil(keep_blocks b / 64) out-of-place tall-skinny GEMMs
+        it replaces (rbl_bench_compress_pass)."""
+        im, sm = np.zeros(1), np.zeros(1)
+        self._check(lib.rbl_bench_compress_pass(self._h, int(rows), int(b), int(m), int(keep_blocks),
+                                                int(reps), dptr(im), dptr(sm)),
+                    "rbl_bench_compress_pass")
+        return float(im[0]), float(sm[0])
+
     def ritz(self, nblocks: int, k: int, S: np.ndarray) -> np.ndarray:
         n, r0, r1, _ = self.matrix_info()
         S = np.asfortranarray(S[: nblocks * self.b, :k], dtype=np.float64)
@@ -623,6 +649,9 @@ class RBLInfo:
     resid: list = field(default_factory=list)   # max residual bound at each check
     trace_A: list = field(default_factory=list)
     trace_B: list = field(default_factory=list)
+    restarts: int = 0            # thick restarts taken (rbl.thick; 0 for an unrestarted run)
+    op_applies: int = 0          # block applications of the operator, the start block included
+    peak_blocks: int = 0         # the most basis blocks held at once
 
 
 def rccl_version() -> dict:
@@ -775,6 +804,8 @@ def lanczos(ctx: Context, k: int, b: int, *, kryl_sz: int = KRYL_SZ_GPU, omega=N
             break
     info.iters = i
     info.nblocks = i                               # Q_1..Q_i (length(Q))
+    info.op_applies = enq + 1                      # A Omega and every enqueued step
+    info.peak_blocks = enq + 1
     D = D[::-1].copy()
     # each Ritz vector's sign: its coefficient column's largest entry positive (host.fix_signs;
     # the eigensolvers disagree on signs, the reference returns dsbev's)

@@ -46,7 +46,8 @@ def _validate_shift(shift, m, n):
 
 
 def RBL_svd(B, k: int, b: int, *, side: str = "auto", omega=None, seed: int = 0,
-            kryl_sz: int = KRYL_SZ_GPU, return_info: bool = False, device: int = 0, shift=None):
+            kryl_sz: int = KRYL_SZ_GPU, return_info: bool = False, device: int = 0, shift=None,
+            max_blocks=None, keep_blocks=None, max_restarts=None):
     """The k largest singular triplets of B (m x n): returns (U, S, V) with S descending,
     U m x k, V n x k, B V = U diag(S).
 
@@ -57,18 +58,38 @@ def RBL_svd(B, k: int, b: int, *, side: str = "auto", omega=None, seed: int = 0,
 
     shift: a pair (u, v), u of length m and v of length n, for the triplets of the rank-one
     shifted C = B - u v^T instead (rbl_set_rect_shift; C is never formed): C V = U diag(S).
-    ``(ones(m), column means)`` is PCA's centring (``RBL_pca``)."""
+    ``(ones(m), column means)`` is PCA's centring (``RBL_pca``).
+
+    max_blocks: when given, the run is the thick-restart loop of ``rbl.thick.lanczos_thick`` on the
+    same operator, in a basis of at most max_blocks + 1 blocks (keep_blocks of them survive a
+    restart, at most max_restarts restarts; kryl_sz is then unused).  None: the unrestarted loop,
+    exactly as without the keyword."""
     m, n = _validate(B, k, side)
     if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b < 1:
         raise ValueError("RBL_svd: b must be an integer >= 1")
     if shift is not None:
         shift = _validate_shift(shift, m, n)
     left = side == "left" or (side == "auto" and m < n)
+    if max_blocks is None:
+        if keep_blocks is not None or max_restarts is not None:
+            raise ValueError("RBL_svd: keep_blocks and max_restarts need max_blocks")
+    else:
+        from .thick import MAX_RESTARTS, check_keep_blocks, lanczos_thick
+        check_keep_blocks(k, b, max_blocks, keep_blocks)
+        if max_blocks * b >= (m if left else n):
+            raise ValueError(f"RBL_svd: max_blocks * b = {max_blocks * b} must be below the iterated "
+                             f"dimension {m if left else n}")
+        if max_restarts is None:
+            max_restarts = MAX_RESTARTS
     with Context(device) as ctx:
         ctx.set_matrix_normal(B.T if left else B)   # CSR <-> CSC views: no host conversion
         if shift is not None:                       # C^T = B^T - v u^T: the pair swaps with the side
             ctx.set_rect_shift(*(shift[::-1] if left else shift))
-        D, V, info = lanczos(ctx, k, b, kryl_sz=kryl_sz, omega=omega, seed=seed)
+        if max_blocks is None:
+            D, V, info = lanczos(ctx, k, b, kryl_sz=kryl_sz, omega=omega, seed=seed)
+        else:
+            D, V, info = lanczos_thick(ctx, k, b, max_blocks=max_blocks, keep_blocks=keep_blocks,
+                                       max_restarts=max_restarts, omega=omega, seed=seed)
         S = np.sqrt(np.maximum(D, 0.0))
         U = ctx.left_vectors(V, S)
     if left:

@@ -533,6 +533,48 @@ int rbl_num_locked(rbl_ctx* ctx);
 int rbl_get_locked(rbl_ctx* ctx, double* V_out);  /* n_local x num_locked column-major */
 int rbl_reorth_last(rbl_ctx* ctx, int nblocks, int flags);
 
+/* ---- thick restart: block Lanczos in a bounded basis ------------------------------------------
+ * (No reference equivalent: restarted.jl restarts from one Ritz vector with explicit locking.)
+ * After m = nblocks steps the run holds A Q = Q T + Q_{m+1} B_{m+1} E_m^T, Q = [Q_1 .. Q_m].  With
+ * the host's T = S Theta S^T, p = keep_blocks * b chosen columns S_p and W = B_{m+1} S_p[last b
+ * rows, :] the Ritz block Y = Q S_p satisfies  A Y = Y Theta_p + Q_{m+1} W  — a Krylov relation
+ * again, over the basis [Y_1 .. Y_kb, Q_{m+1}] with the projected matrix diag(Theta_p) bordered by
+ * W.  rbl_thick_restart turns the basis into that one, in stream order:
+ *   slots 0 .. kb-1 <- [Q_1 .. Q_m] S (S: host, column-major, (m b) x (kb b)), IN PLACE: a workgroup
+ *     owns whole rows and finishes every load of them before its first store, the accumulators of
+ *     all kb b output columns staying in registers (b in {16, 32}: fp64 MFMA, each basis element
+ *     read from HBM once; any other b: one thread per output column) — nothing of size n is
+ *     allocated, which is the point of a memory-bounded run; a fixed summation order, no atomics:
+ *     two calls give the same bits;
+ *   slot kb <- the old slot m (Q_{m+1}), a device copy, bit for bit;
+ *   W (host, column-major, b x (kb b)) is kept on the device for the next step;
+ *   rbl_num_blocks becomes kb + 1, the cached local-reorth Gram is dropped, every step counts as
+ *   fetched: the next legal call is rbl_step / rbl_step_async with i = kb + 1.
+ * That step is the only one with a long recurrence (the "arrow" step):
+ *     U = Op Q_{m+1} - [Y_1 .. Y_kb] W^T,  A_i = Q_{m+1}^T U,  U -= Q_{m+1} A_i,  Q_next B_next = qr(U)
+ * with Op whatever operator is set (sparse on any SpMM kernel, dense, B^T B with or without a
+ * shift, a low-rank update, a Chebyshev filter); the operator runs without its 3-term epilogue,
+ * the subtraction is one tall-skinny GEMM over the kept run, A_i comes from the Gram of the final U
+ * and the local reorth runs as its own pass.  Every later step is the ordinary 3-term step.
+ * rbl_start, setting a matrix and rbl_restart clear a pending arrow step.  The locked set of the
+ * restarted.jl path is untouched.
+ * RBL_COMPRESS_MAX_COLS bounds kb b: a 64-row tile of 512 output columns is 128 fp64 accumulators
+ * per lane over 4 waves, half of the 512 registers a lane has at one wave per SIMD (the rest hold
+ * operands, the prefetched panel and addresses).
+ * Refused before any change (the context stays usable, the basis is unchanged): RBL_ERR_INVALID
+ * for S or W NULL, a non-finite entry of either, keep_blocks outside [1, nblocks), keep_blocks * b >
+ * RBL_COMPRESS_MAX_COLS, or several ranks; RBL_ERR_STATE without an fp64 run, with the fp32 basis,
+ * with a spilled basis (RBL_OPT_DEVICE_BLOCKS), with unfetched asynchronous steps, or when
+ * nblocks + 1 != rbl_num_blocks. */
+#define RBL_COMPRESS_MAX_COLS 512
+int rbl_thick_restart(rbl_ctx* ctx, int nblocks, int keep_blocks, const double* S, const double* W);
+/* Diagnostics: the time per pass (ms, hipEvents, mean over `reps` after one warm-up) of the
+ * in-place compression of m synthetic rows x b blocks to keep_blocks blocks, and of the route
+ * without it: ceil(keep_blocks b / 64) out-of-place tall-skinny GEMMs, each re-reading all m
+ * blocks, into a rows x 64 scratch block.  Everything is allocated and zeroed for the call. */
+int rbl_bench_compress_pass(rbl_ctx* ctx, int64_t rows, int b, int m, int keep_blocks, int reps,
+                            double* inplace_ms, double* sliced_ms);
+
 /* ---- timers --------------------------------------------------------------------------- */
 int rbl_num_stages(void);
 const char* rbl_stage_name(int stage);

@@ -14,6 +14,7 @@
 #   D, V = RBL_hip(A, k, b; basis_bits = 32)      # FLOAT = Float32 mode (common.jl:5)
 #   D, V = RBL_hip(A, k, b; device_blocks = -1)   # hybrid buffer: what fits in HBM, rest on host
 #   D, V = RBL_hip_restarted(A, k)       # restarted.jl:106 (RBL_gpu_restarted)
+#   D, V = RBL_gpu_thick(A, k, b; max_blocks = 24)   # thick restart: a basis of <= 25 blocks
 #   U, D, V = RBL_gpu_svd(B, k, b)       # images.jl:29-33 on a sparse rectangular B, B^T B implicit
 #   U, D, V, mu = RBL_gpu_pca(B, k, b)  # PCA of a sparse B: the triplets of B - 1 mu^T, never formed
 #   D, V = RBL_hip(A, k, b; update = (P, S))   # the operator A + P S P^T, never formed
@@ -314,6 +315,128 @@ function RBL_gpu_deflated(A::Union{SparseMatrixCSC{DOUBLE},Matrix{DOUBLE}}, k::I
         S[j, j] = -D0[j]
     end
     return RBL_hip(A, k, b; timer = timer, basis_bits = 64, update = (V0, S))
+end
+
+# Thick-restart block Lanczos (no reference equivalent; rbl/thick.py lanczos_thick is the same call
+# sequence): the k largest-|lambda| eigenpairs in a basis of at most max_blocks + 1 blocks.  After
+# m = max_blocks steps the host takes the dense projected matrix T = S Theta S', keeps the
+# p = keep_blocks * b pairs of largest |theta|, and rbl_thick_restart turns the basis into
+# [Q S_p, Q_{m+1}] in place (nothing of size n is allocated); T becomes diag(Theta_p) bordered by
+# W = B_{m+1} S_p[end-b+1:end, :], then the block tridiagonal tail.  Step keep_blocks + 1 is the
+# arrow step U = A Q_{m+1} - (Q S_p) W', every later step the ordinary one.  Convergence is the
+# reference's test (common.jl:56-65) on the k wanted pairs, checked where RBL_gpu checks (past k
+# columns, every 4th step) and at the end of each cycle.  update = (P, S): the operator A + P S P'.
+function RBL_gpu_thick(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k::Int64, b::Int64;
+                       max_blocks::Int64, keep_blocks::Int64 = max(cld(k + b, b), min(max_blocks ÷ 2, max_blocks - 2, 512 ÷ b)),
+                       device::Int = 0, seed::UInt64 = rand(UInt64), max_restarts::Int64 = 200,
+                       tol::Float64 = 1e-7, update = nothing)
+    m, kb = max_blocks, keep_blocks
+    kb * b >= k + b || throw(ArgumentError("RBL_gpu_thick: keep_blocks * b must be at least k + b"))
+    kb <= m - 2 || throw(ArgumentError("RBL_gpu_thick: max_blocks must be at least keep_blocks + 2"))
+    kb * b <= 512 || throw(ArgumentError("RBL_gpu_thick: keep_blocks * b exceeds RBL_COMPRESS_MAX_COLS = 512"))
+    n = size(A, 2)
+    m * b < n || throw(ArgumentError("RBL_gpu_thick: max_blocks * b must be below n"))
+    ctx = rbl_context(device)
+    try
+        set_matrix!(ctx, A)
+        update === nothing || set_lowrank!(ctx, Matrix{Float64}(update[1]), Matrix{Float64}(update[2]))
+        rbl_check(ctx, ccall((:rbl_start, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, UInt64),
+                             ctx, Cint(b), Cint(m), Cint(64), C_NULL, seed), "rbl_start")
+        theta = zeros(Float64, 0)
+        W = zeros(Float64, b, 0)
+        head = 0
+        restarts = 0
+        converged = false
+        D = zeros(Float64, 0)
+        S = zeros(Float64, 0, 0)
+        nb = 0
+        # diag(theta), the border W, then the tail: A_t on the diagonal, B_t below it
+        function projected(As, Bs)
+            p = length(theta)
+            N = p + length(As) * b
+            T = zeros(Float64, N, N)
+            for j in 1:p
+                T[j, j] = theta[j]
+            end
+            for t in 1:length(As)
+                o = p + (t - 1) * b
+                T[o+1:o+b, o+1:o+b] = 0.5 .* (As[t] .+ transpose(As[t]))
+                if t == 1 && p > 0
+                    T[o+1:o+b, 1:p] = W
+                    T[1:p, o+1:o+b] = transpose(W)
+                end
+                if t >= 2
+                    T[o+1:o+b, o-b+1:o] = Bs[t-1]
+                    T[o-b+1:o, o+1:o+b] = transpose(Bs[t-1])
+                end
+            end
+            return T
+        end
+        lam = zeros(Float64, 0)
+        Z = zeros(Float64, 0, 0)
+        while true
+            As = Matrix{Float64}[]
+            Bs = Matrix{Float64}[]
+            i = head
+            while i < m
+                j = max(i + 1, 2)
+                while j < m && !(j * b > k && mod(j, 4) == 0)
+                    j += 1
+                end
+                for s in i+1:j
+                    part = (s >= 2 && mod(s, 2) == 0) ? 1 : 0
+                    rbl_check(ctx, ccall((:rbl_step_async, librbl_hip), Cint, (Ptr{Cvoid}, Cint, Cint),
+                                         ctx, Cint(s), Cint(part)), "rbl_step_async")
+                end
+                cnt = j - i
+                Ah = zeros(Float64, b, b, cnt)
+                Bh = zeros(Float64, b, b, cnt)
+                sts = zeros(Cint, cnt)
+                rbl_check(ctx, ccall((:rbl_fetch, librbl_hip), Cint,
+                                     (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
+                                     ctx, Cint(i + 1), Cint(j + 1), Ah, Bh, sts), "rbl_fetch")
+                for t in 1:cnt
+                    push!(As, Ah[:, :, t])
+                    push!(Bs, Bh[:, :, t])
+                end
+                i = j
+                F = eigen(Symmetric(projected(As, Bs)))
+                lam, Z = F.values, F.vectors
+                D, S = sort_eig_abs(lam, Z, min(k, length(lam)))
+                nb = i
+                if length(lam) >= k && check_convergence(Bs[end], S, b, k, tol)
+                    converged = true
+                    break
+                end
+            end
+            (converged || restarts >= max_restarts) && break
+            rbl_check(ctx, ccall((:rbl_reorth_last, librbl_hip), Cint, (Ptr{Cvoid}, Cint, Cint),
+                                 ctx, Cint(m + 1), Cint(1)), "rbl_reorth_last")
+            theta, Sp = sort_eig_abs(lam, Z, kb * b)
+            Sp = Matrix{Float64}(Sp)
+            W = Matrix{Float64}(Bs[end] * Sp[end-b+1:end, :])
+            rbl_check(ctx, ccall((:rbl_thick_restart, librbl_hip), Cint,
+                                 (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}),
+                                 ctx, Cint(m), Cint(kb), Sp, W), "rbl_thick_restart")
+            head = kb
+            restarts += 1
+        end
+        converged || @warn "RBL_gpu_thick: not converged within max_restarts=$max_restarts (best effort)"
+        D = D[end:-1:1]
+        Sr = Matrix{Float64}(S[:, end:-1:1])
+        for c in 1:size(Sr, 2)
+            q = argmax(abs.(Sr[:, c]))
+            Sr[q, c] < 0 && (Sr[:, c] .*= -1)
+        end
+        Vout = zeros(Float64, n, size(Sr, 2))
+        rbl_check(ctx, ccall((:rbl_ritz, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}),
+                             ctx, Cint(nb), Cint(size(Sr, 2)), Sr, Vout), "rbl_ritz")
+        return D, Vout
+    finally
+        ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
+    end
 end
 
 # restarted.jl:106-146 (RBL_gpu_restarted): b = 1 cycles with locking.  The cycle
