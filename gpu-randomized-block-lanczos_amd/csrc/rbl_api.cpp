@@ -26,64 +26,238 @@
 
 using namespace rbl;
 
-struct rbl_ctx {
+// Every device or pinned-host buffer is a DevBuf / PinBuf declared in the struct of its lifetime
+// (MatrixBufs, RunBufs, CtxBufs) and nowhere else: free_matrix and free_run assign an empty struct,
+// so a buffer declared there is released with its lifetime and on every error path.
+namespace rbl::api {
+
+// Owner of one device allocation of `count` T: move-only, released by the destructor, by reset()
+// and by a move assigned over it.  Converts to T*, so it is used where the raw pointer was.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p = o.p;
+      o.p = nullptr;
+    }
+    return *this;
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+  hipError_t alloc(size_t count) {
+    reset();
+    const hipError_t e = hipMalloc(&p, count * sizeof(T));
+    if (e != hipSuccess) p = nullptr;
+    return e;
+  }
+  void reset() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  }
+  void adopt(T* q) {  // takes over an allocation a kernels.hpp routine handed out
+    reset();
+    p = q;
+  }
+  operator T*() const { return p; }
+};
+
+// The pinned-host twin (hipHostMalloc with `flags` / hipHostFree).
+template <class T>
+struct PinBuf {
+  T* p = nullptr;
+  PinBuf() = default;
+  PinBuf(PinBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+  PinBuf& operator=(PinBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p = o.p;
+      o.p = nullptr;
+    }
+    return *this;
+  }
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { reset(); }
+  hipError_t alloc(size_t count, unsigned flags) {
+    reset();
+    const hipError_t e = hipHostMalloc(&p, count * sizeof(T), flags);
+    if (e != hipSuccess) p = nullptr;
+    return e;
+  }
+  void reset() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+  }
+  operator T*() const { return p; }
+};
+
+// A CSR of some rows with the task table of its segmented gather (build_seg): a column tier
+// (CsrDev::seg_tier), the push tier, one orientation of a rectangular B
+struct SegTierBuf {
+  DevBuf<int64_t> rowptr;
+  DevBuf<int32_t> col;
+  DevBuf<double> val;
+  int64_t ntasks = 0, nlong = 0;
+  DevBuf<int64_t> trow;
+  DevBuf<int32_t> tinfo;
+  DevBuf<int64_t> slot_k0;
+  DevBuf<int64_t> lrow;
+  DevBuf<int64_t> lslot;
+  DevBuf<double> scratch;
+};
+
+// ---- buffers that live as long as the matrix (free_matrix); the parts that are also released
+// ---- alone are structs of their own
+
+// column-panel SpMM (spmm_panel.hip; free_panels): per 256-row block its first and last 256-row
+// Q panel
+struct PanelBufs {
+  DevBuf<int32_t> d_panel_blk;
+  DevBuf<uint16_t> d_panel_cnt;  // per block, panel and row: the row's entries in the panel
+  DevBuf<uint32_t> d_panel_st;   // ... and their first record (from the block's base)
+  DevBuf<uint8_t> d_panel_col;   // the records panel-major within a block: column in the panel
+  DevBuf<double> d_panel_val;    //   and value
+};
+
+// segmented-gather task table of the whole CSR (spmm.hip variant 5; CsrDev::seg_*)
+struct SegTableBufs {
+  DevBuf<int64_t> d_seg_trow;
+  DevBuf<int32_t> d_seg_tinfo;
+  DevBuf<int64_t> d_seg_slot_k0;
+  DevBuf<int64_t> d_seg_lrow;
+  DevBuf<int64_t> d_seg_lslot;
+  DevBuf<double> d_seg_scratch;
+};
+
+// column tiers and the indexed halo (free_tiers)
+struct TierBufs {
+  // column tiers of the segmented gather (RBL_SEG_TIERS, one rank; CsrDev::seg_tier): each a
+  // CSR of the same rows holding the nonzeros of one column-degree tier, with its task table
+  SegTierBuf seg_tier[3];
+  DevBuf<int32_t> d_send_idx;  // indexed halo: local row ids the peers asked for, grouped by peer
+  SegTierBuf push_tier;        // push/pull split: tier 1 transposed (rows = ghost slots)
+  DevBuf<int64_t> d_ps_rows;   // own rows that receive partials, ascending
+  DevBuf<int64_t> d_ps_ptr;    //   their slots in d_precv (peer order)
+  DevBuf<int64_t> d_ps_slot;
+};
+
+// rank-one shift C = B - u v^T (rbl_set_rect_shift; free_rect_shift).  d_rect_ts holds t = Q^T v
+// and s = Y^T u (rect_ts_cols doubles each), d_rect_part the workgroup partials of their
+// reductions; both sized by ensure_rect_y
+struct RectShiftBufs {
+  DevBuf<double> d_shift_u;  // m
+  DevBuf<double> d_shift_v;  // n
+  DevBuf<double> d_rect_ts;
+  DevBuf<double> d_rect_part;
+};
+
+// implicit symmetric low-rank update (rbl_set_lowrank; free_lowrank).  d_lr_P: n_local x lr_rp
+// row-major, the columns past lr_r zero (lr_rp = lr_padded_width(lr_r)); d_lr_S: r x r row-major;
+// d_lr_wc holds w = P^T X and c = S w (lr_rp x lr_cols each), d_lr_part the workgroup partials
+// of w; the last two are sized by ensure_lr_bufs
+struct LowrankBufs {
+  DevBuf<double> d_lr_P;
+  DevBuf<double> d_lr_S;
+  DevBuf<double> d_lr_wc;
+  DevBuf<double> d_lr_part;
+};
+
+struct MatrixBufs : PanelBufs, SegTableBufs, TierBufs, RectShiftBufs, LowrankBufs {
+  DevBuf<int64_t> d_rowptr;
+  DevBuf<int32_t> d_col;
+  DevBuf<double> d_val;
+  DevBuf<int64_t> d_tcmin;
+  DevBuf<int64_t> d_tcmax;
+  DevBuf<int64_t> d_tinfo;
+  DevBuf<uint16_t> d_bpos;     // band kernel: per-nonzero dense-tile positions
+  DevBuf<double> d_bt;         // band-tile kernel: the CSR in MFMA-ordered 16-row band tiles
+  DevBuf<uint64_t> d_btp_hdr;  // the band tiles packed (zeros dropped; replaces d_bt)
+  DevBuf<double> d_bth;        // half band tiles (A symmetric; replaces d_bt), and the
+  DevBuf<double> d_bte;        //   first (NG-1)/2 local tiles whole
+  DevBuf<double> d_btp_val;
+  DevBuf<double> d_zrow;       // 32 zeros: band rows the halo does not hold
+  // dense A: local rows in 32-column row-major panels, multiplied by tsmm44 against d_qfull
+  // (all n rows of Q, zero-padded to 32 * dense_panels rows, b <= 64 columns)
+  DevBuf<double> d_dense;
+  DevBuf<double> d_qfull;
+  // rectangular sparse B: [0] B's rows (column ids), [1] B^T's rows (row ids); Y = B Q_i passes
+  // through d_rect_y (m x rect_y_cols)
+  SegTierBuf rect_side[2];
+  DevBuf<double> d_rect_y;
+};
+
+// ---- buffers that live as long as one Krylov run (free_run)
+struct RunBufs {
+  DevBuf<double> d_basis;  // (max_blocks+1) slots (fp64 basis)
+  // pinned host slots of the spilled blocks (block j at h_spill[j - resident]), pinned when
+  // the block is first written out: host memory grows with the blocks a run really spills
+  std::vector<PinBuf<char>> h_spill;
+  DevBuf<double> d_stage;  // one n_local x b staging block for spilled blocks
+  // fp32 basis (mixed precision, RBL_gpu.jl with FLOAT = Float32): slots in d_basis32, the
+  // current and previous block widened to fp64 in d_Qi64 / d_Qm64 for A Q, 3-term and QR
+  DevBuf<float> d_basis32;
+  DevBuf<float> d_stage32;
+  DevBuf<double> d_Qi64;
+  DevBuf<double> d_Qm64;
+  DevBuf<double> d_U;
+  DevBuf<double> d_T;        // scratch n_local x max(b,k)
+  DevBuf<double> d_qext;     // halo-extended Q_i (multi-rank)
+  DevBuf<double> d_sendbuf;  // indexed halo: n_send x b
+  DevBuf<double> d_pushbuf;  // n_ghost x b: pushed partial rows
+  DevBuf<double> d_precv;    // n_send x b: partial rows received for own rows
+  DevBuf<double> d_slab;
+  DevBuf<double> d_C;        // Gram result (<= (max_blocks)*b x 2b)
+  DevBuf<double> d_small;    // R, Rinv, Rtot, Bprev, Ai, G (b x b each)
+  DevBuf<int> d_flags;       // [need3, skip3, status0, status1]
+  PinBuf<double> h_pin;      // pinned staging: Ai, Rtot (2 b x b)
+  PinBuf<double> h_hist;     // rbl_step_async stash: per step i, Ai and Rtot (2 b x b) and the
+                             //   step's 4 flags (2 doubles' room): stash_rec(b) doubles each
+  DevBuf<double> d_stash;    // the device side of one such record (k_stash; RBL_STASH_COPY=1)
+  // locked Ritz vectors of the restarted variants (restarted.jl: Qlock / Qlock_gpu), fp64,
+  // vector j at d_lock + j * nloc (a width-1 panel)
+  DevBuf<double> d_lock;
+  // thick restart: W^T ((kb b) x b row-major) of the pending arrow step, and the compression's S
+  // ((m b) x (kb b) row-major).  Both grow on demand and hold nothing of size n.
+  DevBuf<double> d_arrow_W;
+  DevBuf<double> d_tr_S;
+  // Chebyshev filter: the work blocks of the recurrence beside U, each (n_local + kRowPad) x
+  // filt_cols and zeroed like every block an SpMM writes (d_filt[2] only while a series is set)
+  DevBuf<double> d_filt[3];
+  // Rayleigh-Ritz on A between rbl_ritz_project and rbl_ritz_finish: V = [Q_1..Q_m] S and
+  // W = A V, (n_local + kRowPad) x ritz_kp row-major (ritz_kp = ritz_k rounded up to even)
+  DevBuf<double> d_rv;
+  DevBuf<double> d_rw;
+};
+
+// ---- buffers that live as long as the context (rbl_free)
+struct CtxBufs {
+  PinBuf<char> h_d2h[2];  // pinned slots of the staged D2H (d2h_staged)
+};
+
+}  // namespace rbl::api
+
+struct rbl_ctx : rbl::api::MatrixBufs, rbl::api::RunBufs, rbl::api::CtxBufs {
   int device = 0;
   hipStream_t stream = nullptr;
   int nranks = 1, rank = 0;
-  Comm* comm = nullptr;  // RCCL or in-process transport (comm.hpp); null for one rank
+  rbl::Comm* comm = nullptr;  // RCCL or in-process transport (comm.hpp); null for one rank
   std::string err;
 
   // matrix (local rows [r0,r1) of an n x n symmetric matrix)
   int64_t n = 0, r0 = 0, r1 = 0, nloc = 0, nnz = 0;
-  int64_t* d_rowptr = nullptr;
-  int32_t* d_col = nullptr;
-  double* d_val = nullptr;
-  int64_t* d_tcmin = nullptr;
-  int64_t* d_tcmax = nullptr;
-  int64_t* d_tinfo = nullptr;
-  // column-panel SpMM (spmm_panel.hip): per 256-row block its first and last 256-row Q panel
-  int32_t* d_panel_blk = nullptr;
-  uint16_t* d_panel_cnt = nullptr;  // per block, panel and row: the row's entries in the panel
-  uint32_t* d_panel_st = nullptr;   // ... and their first record (from the block's base)
-  uint8_t* d_panel_col = nullptr;   // the records panel-major within a block: column in the panel
-  double* d_panel_val = nullptr;    //   and value
   int64_t panel_nblk = 0;
   int panel_rpg = 4;        // rows per 16-lane group: blocks of 64 panel_rpg rows
   int panel_ch = 48;        // records per row and chunk load
   bool panel_auto = false;  // chosen by default: every staged Q row used >= 4 times on average
   int64_t panel_span = 0;   // the widest block window, Q rows
-  uint16_t* d_bpos = nullptr;  // band kernel: per-nonzero dense-tile positions
-  double* d_bt = nullptr;      // band-tile kernel: the CSR in MFMA-ordered 16-row band tiles
-  int bt_ng = 0;               // its band groups (0: not applicable)
-  uint64_t* d_btp_hdr = nullptr;  // the band tiles packed (zeros dropped; replaces d_bt)
-  double* d_bth = nullptr;        // half band tiles (A symmetric; replaces d_bt), and the
-  double* d_bte = nullptr;        //   first (NG-1)/2 local tiles whole
-  double* d_btp_val = nullptr;
-  double* d_zrow = nullptr;    // 32 zeros: band rows the halo does not hold
-  // segmented-gather task table (spmm.hip variant 5; CsrDev::seg_*)
+  int bt_ng = 0;            // the band groups of d_bt (0: not applicable)
   int64_t seg_ntasks = 0, seg_nlong = 0;
-  int64_t* d_seg_trow = nullptr;
-  int32_t* d_seg_tinfo = nullptr;
-  int64_t* d_seg_slot_k0 = nullptr;
-  int64_t* d_seg_lrow = nullptr;
-  int64_t* d_seg_lslot = nullptr;
-  double* d_seg_scratch = nullptr;
-  // column tiers of the segmented gather (RBL_SEG_TIERS, one rank; CsrDev::seg_tier): each a
-  // CSR of the same rows holding the nonzeros of one column-degree tier, with its task table
-  struct SegTierBuf {
-    int64_t* rowptr = nullptr;
-    int32_t* col = nullptr;
-    double* val = nullptr;
-    int64_t ntasks = 0, nlong = 0;
-    int64_t* trow = nullptr;
-    int32_t* tinfo = nullptr;
-    int64_t* slot_k0 = nullptr;
-    int64_t* lrow = nullptr;
-    int64_t* lslot = nullptr;
-    double* scratch = nullptr;
-  };
   int seg_ntiers = 0;
-  SegTierBuf seg_tier[3];
   bool seg_split = false;             // several ranks: tiers = own / halo columns
   // indexed halo (with seg_split): the halo tier's columns renumbered to ghost slots
   // [0, n_ghost) in d_qext, grouped by owning rank; each step every rank packs the rows its
@@ -91,9 +265,7 @@ struct rbl_ctx {
   bool ghost = false;
   int64_t n_ghost = 0, n_send = 0;
   std::vector<int64_t> ghost_cnt, ghost_off, send_cnt, send_off;
-  int32_t* d_send_idx = nullptr;
-  double* d_sendbuf = nullptr;        // n_send x b, per run
-  const double* ghost_local = nullptr;  // the block the last exchange sent from
+  const double* ghost_local = nullptr;  // alias: the block the last exchange sent from
   bool ghost_active = false;          // the last exchange was the indexed one (use_ghost)
   bool halo_overlap = true;           // RBL_OPT_HALO_OVERLAP
   // push/pull split of the indexed halo (RBL_OPT_HALO_PUSH): of every off-rank product
@@ -104,54 +276,28 @@ struct rbl_ctx {
   // added to U in peer order (d_ps_*)
   int halo_push_opt = 2;              // 0 off, 1 on, 2 on when it moves fewer rows (default)
   bool push = false;
-  SegTierBuf push_tier;
   int64_t push_rows = 0;              // = n_ghost (rows of the push tier)
-  double* d_pushbuf = nullptr;        // n_ghost x b: pushed partial rows (per run)
-  double* d_precv = nullptr;          // n_send x b: partial rows received for own rows (per run)
-  int64_t* d_ps_rows = nullptr;       // own rows that receive partials, ascending
-  int64_t* d_ps_ptr = nullptr;        //   their slots in d_precv (peer order)
-  int64_t* d_ps_slot = nullptr;
   int64_t n_ps_rows = 0;
   size_t push_cap = 0;                // capacity (doubles) of d_pushbuf / d_precv
   int64_t push_pred_rows = 0, pull_pred_rows = 0;  // rows per SpMM, summed over ranks (setup)
   hipEvent_t ev_push_ready = nullptr, ev_push_done = nullptr;
   hipStream_t hstream = nullptr;      // the overlapped halo exchange
   hipEvent_t ev_qready = nullptr, ev_halo = nullptr;
-  // dense A (RBL_gpu(A::Matrix{Float64})): local rows in 32-column row-major panels
-  // (panel p = columns [32p, 32p+32), zero past n), multiplied by tsmm44 against d_qfull
-  // (all n rows of Q, zero-padded to 32 * dense_panels rows, b <= 64 columns)
+  // dense A (RBL_gpu(A::Matrix{Float64})): panel p = columns [32p, 32p+32), zero past n
   bool dense = false;
-  double* d_dense = nullptr;
   int64_t dense_panels = 0;
-  double* d_qfull = nullptr;
   int qfull_cols = 0;         // columns d_qfull was sized for
   // rectangular sparse B, m x n (rbl_set_matrix_normal): both orientations as CSR with their
-  // task tables — [0] B's rows (column ids), [1] B^T's rows (row ids) — for the gather pair of
-  // spmm_rect.hip; the Krylov operator is B^T B on n rows, Y = B Q_i passes through d_rect_y
+  // task tables for the gather pair of spmm_rect.hip; the Krylov operator is B^T B on n rows
   bool rect = false;
   int64_t rect_m = 0;
-  SegTierBuf rect_side[2];
-  double* d_rect_y = nullptr;  // m x rect_y_cols
   int rect_y_cols = 0;
-  // rank-one shift C = B - u v^T (rbl_set_rect_shift): the operator is then C^T C.  d_rect_ts
-  // holds t = Q^T v and s = Y^T u (rect_ts_cols doubles each), d_rect_part the workgroup
-  // partials of their reductions; both sized by ensure_rect_y
+  // rank-one shift C = B - u v^T (rbl_set_rect_shift): the operator is then C^T C
   bool rect_shift = false;
-  double* d_shift_u = nullptr;  // m
-  double* d_shift_v = nullptr;  // n
-  double* d_rect_ts = nullptr;
-  double* d_rect_part = nullptr;
   int rect_ts_cols = 0;
   // implicit symmetric low-rank update (rbl_set_lowrank): the operator is A + P S P^T, applied
-  // by apply_A after the SpMM.  d_lr_P: n_local x lr_rp row-major, the columns past lr_r zero
-  // (lr_rp = lr_padded_width(lr_r)); d_lr_S: r x r row-major; d_lr_wc holds w = P^T X and
-  // c = S w (lr_rp x lr_cols each), d_lr_part the workgroup partials of w; the last two are
-  // sized by ensure_lr_bufs
+  // by apply_A after the SpMM
   int lr_r = 0, lr_rp = 0;
-  double* d_lr_P = nullptr;
-  double* d_lr_S = nullptr;
-  double* d_lr_wc = nullptr;
-  double* d_lr_part = nullptr;
   int lr_cols = 0;
   int64_t ntiles = 0, tiles_per_wg = 0;
   bool window_ok16 = false, window_ok32 = false;
@@ -166,15 +312,12 @@ struct rbl_ctx {
   bool keep_csr = true;                   // RBL_OPT_KEEP_CSR
   int relabel_opt = 0;                    // RBL_OPT_RELABEL (applies to the next generator call)
   bool relabeled = false;                 // the matrix held is P A P^T (rmat generator)
-  Scatter relabel_perm;                   //   with this P: vertex v at row perm(v)
+  rbl::Scatter relabel_perm;              //   with this P: vertex v at row perm(v)
   bool csr_dropped = false;               // values / column ids released (band tiles only)
 
   // Krylov run
   int b = 0, max_blocks = 0, nblocks = 0;
-  double* d_basis = nullptr;  // (max_blocks+1) slots (fp64 basis)
   int64_t slot = 0;           // nloc * b
-  // fp32 basis (mixed precision, RBL_gpu.jl with FLOAT = Float32): slots in d_basis32, the
-  // current and previous block widened to fp64 in d_Qi64 / d_Qm64 for A Q, 3-term and QR
   int basis_bits = 64;
   // host spill (RBL_OPT_DEVICE_BLOCKS): blocks j < resident live in d_basis slot j; blocks
   // j >= resident in working slot resident + (j & 1) while among the two newest, and in
@@ -182,76 +325,43 @@ struct rbl_ctx {
   int dev_blocks_opt = 0;
   bool auto_planned = false;  // the current basis plan came from RBL_OPT_DEVICE_BLOCKS = -1
   int resident = INT32_MAX;
-  // pinned host slots of the spilled blocks (block j at h_spill[j - resident]), pinned when
-  // the block is first written out: host memory grows with the blocks a run really spills
-  std::vector<void*> h_spill;
-  double* d_stage = nullptr;          // one n_local x b staging block for spilled blocks
   hipStream_t cstream = nullptr;      // D2H copies of finished spilled blocks
   hipEvent_t ev_fin = nullptr, ev_d2h[2] = {nullptr, nullptr};
   // rbl_step_async: step i's stash (A_i, R_tot, flags) has landed when step_ev[i] completes, so
   // rbl_fetch waits for the steps it returns, not for steps enqueued after them
   std::vector<hipEvent_t> step_ev;
   bool d2h_pending[2] = {false, false};
-  float* d_basis32 = nullptr;
-  float* d_stage32 = nullptr;
-  double* d_Qi64 = nullptr;
-  double* d_Qm64 = nullptr;
-  double* d_U = nullptr;
-  double* d_T = nullptr;      // scratch n_local x max(b,k)
   int64_t T_cols = 0;
-  double* d_qext = nullptr;   // halo-extended Q_i (multi-rank)
-  size_t qext_cap = 0;        // its capacity in doubles (grown by ensure_qext)
-  double* d_slab = nullptr;
+  size_t qext_cap = 0;        // capacity of d_qext in doubles (grown by ensure_qext)
   size_t slab_elems = 0;
-  double* d_C = nullptr;      // Gram result (<= (max_blocks)*b x 2b)
   size_t C_elems = 0;
-  double* d_small = nullptr;  // R, Rinv, Rtot, Bprev, Ai, G (b x b each)
-  int* d_flags = nullptr;     // [need3, skip3, status0, status1]
-  double* h_pin = nullptr;    // pinned staging: Ai, Rtot (2 b x b)
-  void* h_d2h[2] = {nullptr, nullptr};  // pinned slots of the staged D2H (d2h_staged)
   hipEvent_t ev_d2h_slot[2] = {nullptr, nullptr};
   hipStream_t rstream = nullptr;      // the Ritz row pieces (ritz_pipelined)
   hipEvent_t ev_ritz[9] = {};         // S uploaded, then each row piece finished on rstream
-  double* h_hist = nullptr;   // rbl_step_async stash: per step i, Ai and Rtot (2 b x b) and the
-                              //   step's 4 flags (2 doubles' room): stash_rec(b) doubles each
-  double* d_stash = nullptr;  // the device side of one such record (k_stash; RBL_STASH_COPY=1)
   // k_stash writes the record straight into h_pin / h_hist (coherent pinned memory, these are
   // their device addresses) instead of a device record plus a D2H copy, which the SDMA engine
   // ran ~60-80 us after the kernel, on the step's critical path
   bool stash_direct = true;
-  double* dv_pin = nullptr;
-  double* dv_hist = nullptr;
+  double* dv_pin = nullptr;   // alias: the device address of h_pin
+  double* dv_hist = nullptr;  // alias: the device address of h_hist
   bool flags_clean = false;   // d_flags already zero (the last step's k_stash cleared them)
   int fetched = 1;            // steps < fetched have been returned by rbl_fetch
   bool have_bprev = false;
-  // locked Ritz vectors of the restarted variants (restarted.jl: Qlock / Qlock_gpu), fp64,
-  // vector j at d_lock + j * nloc (a width-1 panel)
-  double* d_lock = nullptr;
   int nlock = 0, lock_cap = 0;
   // thick restart (rbl_thick_restart): arrow_kb > 0 while the arrow step is pending — the basis is
-  // [Y_1 .. Y_kb, Q_{m+1}] and step kb + 1 forms U = Op Q_{m+1} - [Y_1 .. Y_kb] W^T with W^T
-  // ((kb b) x b row-major) in d_arrow_W; d_tr_S holds the compression's S ((m b) x (kb b)
-  // row-major).  Both grow on demand and hold nothing of size n.
+  // [Y_1 .. Y_kb, Q_{m+1}] and step kb + 1 forms U = Op Q_{m+1} - [Y_1 .. Y_kb] W^T
   int arrow_kb = 0;
-  double* d_arrow_W = nullptr;
-  double* d_tr_S = nullptr;
   size_t arrow_W_cap = 0, tr_S_cap = 0;
   // Chebyshev filter (rbl_set_filter; degree 0: none): the Krylov operator is p(A), applied by a
-  // three-term recurrence through two work blocks beside U, each (n_local + kRowPad) x filt_cols
-  // and zeroed like every block an SpMM writes; sized at rbl_start
+  // three-term recurrence through the work blocks d_filt, sized at rbl_start
   int filt_deg = 0;
   double filt_lo = 0.0, filt_hi = 0.0, filt_ref = 0.0;
-  double* d_filt[3] = {nullptr, nullptr, nullptr};
   int filt_cols = 0;
   // Chebyshev series (rbl_set_filter_series; empty: none): p(A) = sum_j ser_mu[j] T_j((A - c)/e)
-  // over [ser_lo, ser_hi]; its recurrence rotates through three work blocks (d_filt[2] is
-  // allocated only while a series is set).  At most one of filt_deg > 0 and a series holds.
+  // over [ser_lo, ser_hi]; its recurrence rotates through three work blocks.  At most one of
+  // filt_deg > 0 and a series holds.
   std::vector<double> ser_mu;
   double ser_lo = 0.0, ser_hi = 0.0;
-  // Rayleigh-Ritz on A between rbl_ritz_project and rbl_ritz_finish: V = [Q_1..Q_m] S and
-  // W = A V, (n_local + kRowPad) x ritz_kp row-major (ritz_kp = ritz_k rounded up to even)
-  double* d_rv = nullptr;
-  double* d_rw = nullptr;
   int ritz_k = 0;
 
   // options
@@ -286,6 +396,8 @@ struct rbl_ctx {
   size_t ev_used = 0;
 };
 
+using namespace rbl::api;
+
 namespace {
 
 const char* kStageNames[RBL_NUM_STAGES] = {"AQ", "3-term", "qr", "part reorth", "loc reorth",
@@ -296,17 +408,6 @@ int fail(rbl_ctx* c, int code, const std::string& msg) {
   return code;
 }
 
-// device allocation released on every return path
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  double* d() const { return static_cast<double*>(p); }
-};
 
 #define HIPC(expr)                                                                    \
   do {                                                                                \
@@ -347,11 +448,10 @@ const double* block_dev(rbl_ctx* ctx, int j, int nblocks, int* st) {
 // pin the host slot of spilled block j on first use (non-coherent pages: the DMA engines
 // stream them at PCIe rate both ways)
 int spill_slot(rbl_ctx* ctx, int j, size_t elem) {
-  void*& h = ctx->h_spill[j - ctx->resident];
+  auto& h = ctx->h_spill[j - ctx->resident];
   if (!h) {
-    const hipError_t e = hipHostMalloc(&h, (size_t)ctx->slot * elem, hipHostMallocNonCoherent);
+    const hipError_t e = h.alloc((size_t)ctx->slot * elem, hipHostMallocNonCoherent);
     if (e != hipSuccess) {
-      h = nullptr;
       return fail(ctx, e == hipErrorOutOfMemory ? RBL_ERR_OOM : RBL_ERR_HIP,
                   std::string("host spill: hipHostMalloc: ") + hipGetErrorString(e));
     }
@@ -443,7 +543,7 @@ CsrDev csr(rbl_ctx* ctx) {
 // <= kSegPack nonzeros and <= 64 rows, rows over kSegLen nonzeros cut into segments.  The
 // rectangular gather pair (spmm_rect.hip) builds its two tables here with its own limits and
 // scratch_w = 64 doubles per segment slot.
-int build_seg(rbl_ctx* ctx, const std::vector<int64_t>& rp, rbl_ctx::SegTierBuf& out,
+int build_seg(rbl_ctx* ctx, const std::vector<int64_t>& rp, SegTierBuf& out,
               int64_t seg_len = kSegLen, int64_t pack = kSegPack, int scratch_w = 32) {
   const int64_t m = (int64_t)rp.size() - 1;
   if (m <= 0) return RBL_OK;
@@ -482,12 +582,12 @@ int build_seg(rbl_ctx* ctx, const std::vector<int64_t>& rp, rbl_ctx::SegTierBuf&
   slot_k0.push_back(INT64_MAX);
   out.ntasks = (int64_t)trow.size();
   out.nlong = (int64_t)lrow.size();
-  HIPC(hipMalloc(&out.trow, trow.size() * sizeof(int64_t)));
-  HIPC(hipMalloc(&out.tinfo, tinfo.size() * sizeof(int32_t)));
-  HIPC(hipMalloc(&out.slot_k0, slot_k0.size() * sizeof(int64_t)));
-  HIPC(hipMalloc(&out.lslot, lslot.size() * sizeof(int64_t)));
-  HIPC(hipMalloc(&out.lrow, std::max<size_t>(lrow.size(), 1) * sizeof(int64_t)));
-  HIPC(hipMalloc(&out.scratch, std::max<size_t>(slot_k0.size() - 1, 1) * scratch_w * sizeof(double)));
+  HIPC(out.trow.alloc(trow.size()));
+  HIPC(out.tinfo.alloc(tinfo.size()));
+  HIPC(out.slot_k0.alloc(slot_k0.size()));
+  HIPC(out.lslot.alloc(lslot.size()));
+  HIPC(out.lrow.alloc(std::max<size_t>(lrow.size(), 1)));
+  HIPC(out.scratch.alloc(std::max<size_t>(slot_k0.size() - 1, 1) * scratch_w));
   HIPC(hipMemcpy(out.trow, trow.data(), trow.size() * sizeof(int64_t), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(out.tinfo, tinfo.data(), tinfo.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(out.slot_k0, slot_k0.data(), slot_k0.size() * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -497,59 +597,37 @@ int build_seg(rbl_ctx* ctx, const std::vector<int64_t>& rp, rbl_ctx::SegTierBuf&
   return RBL_OK;
 }
 
-void free_seg(rbl_ctx::SegTierBuf& T, bool with_csr) {
-  if (with_csr) {
-    hipFree(T.rowptr);
-    hipFree(T.col);
-    hipFree(T.val);
-  }
-  hipFree(T.trow);
-  hipFree(T.tinfo);
-  hipFree(T.slot_k0);
-  hipFree(T.lrow);
-  hipFree(T.lslot);
-  hipFree(T.scratch);
-  T = rbl_ctx::SegTierBuf();
-}
-
 // the column-panel format (spmm_panel.hip) and its choice
 void free_panels(rbl_ctx* ctx) {
-  hipFree(ctx->d_panel_blk); ctx->d_panel_blk = nullptr; ctx->panel_nblk = 0; ctx->panel_auto = false;
+  static_cast<PanelBufs&>(*ctx) = PanelBufs{};
+  ctx->panel_nblk = 0;
+  ctx->panel_auto = false;
   ctx->panel_span = 0;
-  hipFree(ctx->d_panel_cnt); ctx->d_panel_cnt = nullptr;
-  hipFree(ctx->d_panel_st); ctx->d_panel_st = nullptr;
-  hipFree(ctx->d_panel_col); ctx->d_panel_col = nullptr;
-  hipFree(ctx->d_panel_val); ctx->d_panel_val = nullptr;
 }
 
 void free_tiers(rbl_ctx* ctx) {
-  for (auto& T : ctx->seg_tier) free_seg(T, true);
+  static_cast<TierBufs&>(*ctx) = TierBufs{};
   ctx->seg_ntiers = 0;
   ctx->seg_split = false;
-  hipFree(ctx->d_send_idx); ctx->d_send_idx = nullptr;
   ctx->ghost = false;
   ctx->n_ghost = ctx->n_send = 0;
-  free_seg(ctx->push_tier, true);
   ctx->push = false;
   ctx->push_rows = 0;
-  hipFree(ctx->d_ps_rows); ctx->d_ps_rows = nullptr;
-  hipFree(ctx->d_ps_ptr); ctx->d_ps_ptr = nullptr;
-  hipFree(ctx->d_ps_slot); ctx->d_ps_slot = nullptr;
   ctx->n_ps_rows = 0;
 }
 
 int prepare_segments(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
   if (ctx->nloc <= 0 || ctx->nnz <= 0) return RBL_OK;
-  rbl_ctx::SegTierBuf T;
+  SegTierBuf T;
   const int st = build_seg(ctx, rp, T);
   ctx->seg_ntasks = T.ntasks;
   ctx->seg_nlong = T.nlong;
-  ctx->d_seg_trow = T.trow;
-  ctx->d_seg_tinfo = T.tinfo;
-  ctx->d_seg_slot_k0 = T.slot_k0;
-  ctx->d_seg_lrow = T.lrow;
-  ctx->d_seg_lslot = T.lslot;
-  ctx->d_seg_scratch = T.scratch;
+  ctx->d_seg_trow = std::move(T.trow);
+  ctx->d_seg_tinfo = std::move(T.tinfo);
+  ctx->d_seg_slot_k0 = std::move(T.slot_k0);
+  ctx->d_seg_lrow = std::move(T.lrow);
+  ctx->d_seg_lslot = std::move(T.lslot);
+  ctx->d_seg_scratch = std::move(T.scratch);
   return st;
 }
 
@@ -566,19 +644,19 @@ int64_t tier_nnz(rbl_ctx* ctx, int t) {
 
 // Indexed halo: the columns this rank references outside its rows become ghost slots (sorted by
 // global id, so grouped by owner); the ranks exchange how many rows, then which rows, each asks
-// of each; *d_map (device, n int32) maps a ghost column to its slot (caller frees).
-int build_ghosts(rbl_ctx* ctx, int32_t** d_map, const int32_t* cols, int64_t ncols) {
+// of each; d_map (device, n int32) maps a ghost column to its slot.
+int build_ghosts(rbl_ctx* ctx, DevBuf<int32_t>& d_map, const int32_t* cols, int64_t ncols) {
   const int P = ctx->nranks, me = ctx->rank;
   const int64_t n = ctx->n;
-  uint8_t* d_mark = nullptr;
-  HIPC(hipMalloc(&d_mark, std::max<int64_t>(n, 1)));
+  DevBuf<uint8_t> d_mark;
+  HIPC(d_mark.alloc(std::max<int64_t>(n, 1)));
   HIPC(hipMemsetAsync(d_mark, 0, n, ctx->stream));
   mark_cols(cols, ncols, ctx->r0, ctx->r1, d_mark, ctx->stream);
   HIPC(hipGetLastError());
   std::vector<uint8_t> mark(n);
   HIPC(hipMemcpyAsync(mark.data(), d_mark, n, hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(d_mark);
+  d_mark.reset();  // n bytes, before the host map and d_map of n int32 each
   std::vector<int32_t> map(n, 0);
   std::vector<int64_t> req;  // global ids of the ghost rows, ascending
   ctx->ghost_cnt.assign(P, 0);
@@ -607,22 +685,22 @@ int build_ghosts(rbl_ctx* ctx, int32_t** d_map, const int32_t* cols, int64_t nco
   }
   ctx->n_send = ns;
   // the request lists themselves, int64 ids carried as 8-byte words by the halo transport
-  DevBuf d_req, d_got;
-  HIPC(hipMalloc(&d_req.p, std::max<int64_t>(ctx->n_ghost, 1) * sizeof(int64_t)));
-  HIPC(hipMalloc(&d_got.p, std::max<int64_t>(ns, 1) * sizeof(int64_t)));
+  DevBuf<int64_t> d_req, d_got;
+  HIPC(d_req.alloc(std::max<int64_t>(ctx->n_ghost, 1)));
+  HIPC(d_got.alloc(std::max<int64_t>(ns, 1)));
   if (ctx->n_ghost)
-    HIPC(hipMemcpy(d_req.p, req.data(), ctx->n_ghost * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_req, req.data(), ctx->n_ghost * sizeof(int64_t), hipMemcpyHostToDevice));
   std::vector<Comm::Xfer> x(P);
   for (int q = 0; q < P; ++q) {
     if (q == me) continue;
-    x[q].send = d_req.d() + ctx->ghost_off[q];
+    x[q].send = reinterpret_cast<const double*>(d_req + ctx->ghost_off[q]);
     x[q].nsend = (size_t)ctx->ghost_cnt[q];
-    x[q].recv = d_got.d() + ctx->send_off[q];
+    x[q].recv = reinterpret_cast<double*>(d_got + ctx->send_off[q]);
     x[q].nrecv = (size_t)ctx->send_cnt[q];
   }
   COMMC(ctx->comm->exchange(x, ctx->stream, &ctx->err));
   std::vector<int64_t> got(std::max<int64_t>(ns, 1));
-  HIPC(hipMemcpyAsync(got.data(), d_got.p, ns * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(got.data(), d_got, ns * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   std::vector<int32_t> idx(std::max<int64_t>(ns, 1), 0);
   for (int64_t i = 0; i < ns; ++i) {
@@ -630,10 +708,10 @@ int build_ghosts(rbl_ctx* ctx, int32_t** d_map, const int32_t* cols, int64_t nco
     if (g < 0 || g >= ctx->nloc) return fail(ctx, RBL_ERR_INVALID, "indexed halo: a peer asked for a row I do not own");
     idx[i] = (int32_t)g;
   }
-  HIPC(hipMalloc(&ctx->d_send_idx, std::max<int64_t>(ns, 1) * sizeof(int32_t)));
+  HIPC(ctx->d_send_idx.alloc(std::max<int64_t>(ns, 1)));
   if (ns) HIPC(hipMemcpy(ctx->d_send_idx, idx.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIPC(hipMalloc(d_map, std::max<int64_t>(n, 1) * sizeof(int32_t)));
-  HIPC(hipMemcpy(*d_map, map.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPC(d_map.alloc(std::max<int64_t>(n, 1)));
+  HIPC(hipMemcpy(d_map, map.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
   return RBL_OK;
 }
 
@@ -663,11 +741,11 @@ int prepare_push(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
     for (int64_t i = 0; i < ctx->bounds[q + 1] - ctx->bounds[q]; ++i)
       deg[ctx->bounds[q] + i] = (int32_t)std::min<int64_t>(all[(size_t)q * w + i], INT32_MAX);
   std::vector<int64_t>().swap(all);
-  DevBuf d_deg;
-  HIPC(hipMalloc(&d_deg.p, deg.size() * sizeof(int32_t)));
-  HIPC(hipMemcpy(d_deg.p, deg.data(), deg.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  DevBuf<int32_t> d_deg;
+  HIPC(d_deg.alloc(deg.size()));
+  HIPC(hipMemcpy(d_deg, deg.data(), deg.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   TierRule R;
-  R.deg = static_cast<const int32_t*>(d_deg.p);
+  R.deg = d_deg;
   R.row0 = ctx->r0;
   R.r0 = ctx->r0;
   R.r1 = ctx->r1;
@@ -755,14 +833,13 @@ int prepare_push(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
   }
   if (ctx->halo_push_opt == 2 && !(2.0 * (double)d1 < 0.85 * (double)d12)) return 0;
   // split: tier 2 dropped, the ghosts are tier 1's columns
-  free_seg(ctx->seg_tier[2], true);
+  ctx->seg_tier[2] = SegTierBuf();
   ctx->seg_ntiers = 2;
-  int32_t* d_map = nullptr;
-  CHK(build_ghosts(ctx, &d_map, ctx->seg_tier[1].col, nz1));
+  DevBuf<int32_t> d_map;
+  CHK(build_ghosts(ctx, d_map, ctx->seg_tier[1].col, nz1));
   if (nz1) remap_cols(ctx->seg_tier[1].col, nz1, d_map, ctx->stream);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(d_map);
   ctx->seg_split = true;
   ctx->ghost = true;
   // the push tier: tier 1 transposed, rows = ghost slots (in row order within a slot)
@@ -787,9 +864,9 @@ int prepare_push(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
       pv[at] = v1[k];
     }
   auto& T = ctx->push_tier;
-  HIPC(hipMalloc(&T.rowptr, (G + 1) * sizeof(int64_t)));
-  HIPC(hipMalloc(&T.col, (nz1 + kCsrPad) * sizeof(int32_t)));
-  HIPC(hipMalloc(&T.val, (nz1 + kCsrPad) * sizeof(double)));
+  HIPC(T.rowptr.alloc(G + 1));
+  HIPC(T.col.alloc(nz1 + kCsrPad));
+  HIPC(T.val.alloc(nz1 + kCsrPad));
   HIPC(hipMemset(T.col, 0, (nz1 + kCsrPad) * sizeof(int32_t)));
   HIPC(hipMemset(T.val, 0, (nz1 + kCsrPad) * sizeof(double)));
   HIPC(hipMemcpy(T.rowptr, prp.data(), (G + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -817,9 +894,9 @@ int prepare_push(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
       ptr.push_back(cnt[r + 1]);
     }
   ctx->n_ps_rows = (int64_t)rows.size();
-  HIPC(hipMalloc(&ctx->d_ps_rows, std::max<size_t>(rows.size(), 1) * sizeof(int64_t)));
-  HIPC(hipMalloc(&ctx->d_ps_ptr, ptr.size() * sizeof(int64_t)));
-  HIPC(hipMalloc(&ctx->d_ps_slot, slot.size() * sizeof(int64_t)));
+  HIPC(ctx->d_ps_rows.alloc(std::max<size_t>(rows.size(), 1)));
+  HIPC(ctx->d_ps_ptr.alloc(ptr.size()));
+  HIPC(ctx->d_ps_slot.alloc(slot.size()));
   if (!rows.empty())
     HIPC(hipMemcpy(ctx->d_ps_rows, rows.data(), rows.size() * sizeof(int64_t), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(ctx->d_ps_ptr, ptr.data(), ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -863,8 +940,8 @@ int prepare_tiers(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
       if (ps == 1) return RBL_OK;
       free_tiers(ctx);
     }
-    int32_t* d_map = nullptr;
-    CHK(build_ghosts(ctx, &d_map, ctx->d_col, ctx->nnz));
+    DevBuf<int32_t> d_map;
+    CHK(build_ghosts(ctx, d_map, ctx->d_col, ctx->nnz));
     const int st = build_tiers(ctx, tier_of, 2);
     if (st == RBL_OK) {
       remap_cols(ctx->seg_tier[1].col, ctx->seg_tier[1].ntasks > 0 ? tier_nnz(ctx, 1) : 0, d_map,
@@ -872,7 +949,6 @@ int prepare_tiers(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
       HIPC(hipGetLastError());
       HIPC(hipStreamSynchronize(ctx->stream));
     }
-    hipFree(d_map);
     CHK(st);
     ctx->seg_split = true;
     ctx->ghost = true;
@@ -921,10 +997,10 @@ int prepare_tiers(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
 // the per-nonzero rule of the push/pull halo split (rule, nt = 3).
 int build_tiers(rbl_ctx* ctx, const std::vector<uint8_t>& tier_of, int nt, const TierRule* rule) {
   const int64_t n = ctx->n, m = ctx->nloc;
-  uint8_t* d_tier = nullptr;
-  int32_t* d_cnt = nullptr;
-  HIPC(hipMalloc(&d_tier, rule ? 1 : n));
-  HIPC(hipMalloc(&d_cnt, std::max<size_t>((size_t)nt * m, 1) * sizeof(int32_t)));
+  DevBuf<uint8_t> d_tier;
+  DevBuf<int32_t> d_cnt;
+  HIPC(d_tier.alloc(rule ? 1 : n));
+  HIPC(d_cnt.alloc(std::max<size_t>((size_t)nt * m, 1)));
   if (rule)
     seg_tier_count_rule(m, ctx->d_rowptr, ctx->d_col, *rule, d_cnt, ctx->stream);
   else {
@@ -943,9 +1019,9 @@ int build_tiers(rbl_ctx* ctx, const std::vector<uint8_t>& tier_of, int nt, const
     for (int64_t r = 0; r < m; ++r) trp[t][r + 1] = trp[t][r] + cnt[(size_t)t * m + r];
     auto& T = ctx->seg_tier[t];
     const int64_t nz = trp[t][m];
-    HIPC(hipMalloc(&T.rowptr, (m + 1) * sizeof(int64_t)));
-    HIPC(hipMalloc(&T.col, (nz + kCsrPad) * sizeof(int32_t)));
-    HIPC(hipMalloc(&T.val, (nz + kCsrPad) * sizeof(double)));
+    HIPC(T.rowptr.alloc(m + 1));
+    HIPC(T.col.alloc(nz + kCsrPad));
+    HIPC(T.val.alloc(nz + kCsrPad));
     HIPC(hipMemset(T.col + nz, 0, kCsrPad * sizeof(int32_t)));
     HIPC(hipMemset(T.val + nz, 0, kCsrPad * sizeof(double)));
     HIPC(hipMemcpy(T.rowptr, trp[t].data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -960,18 +1036,7 @@ int build_tiers(rbl_ctx* ctx, const std::vector<uint8_t>& tier_of, int nt, const
     seg_tier_fill(m, ctx->d_rowptr, ctx->d_col, ctx->d_val, d_tier, nt, rpp, colp, valp, ctx->stream);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(d_tier);
-  hipFree(d_cnt);
-  for (int t = 0; t < nt; ++t) {
-    auto& T = ctx->seg_tier[t];
-    int64_t* rp_keep = T.rowptr;
-    int32_t* col_keep = T.col;
-    double* val_keep = T.val;
-    CHK(build_seg(ctx, trp[t], T));
-    T.rowptr = rp_keep;
-    T.col = col_keep;
-    T.val = val_keep;
-  }
+  for (int t = 0; t < nt; ++t) CHK(build_seg(ctx, trp[t], ctx->seg_tier[t]));
   return RBL_OK;
 }
 
@@ -998,8 +1063,8 @@ int prepare_window_formats(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
   ctx->ntiles = (ctx->nloc + kWindowTileRows - 1) / kWindowTileRows;
   if (ctx->ntiles == 0 || ctx->nnz == 0) return RBL_OK;
   const int64_t nt = ctx->ntiles;
-  HIPC(hipMalloc(&ctx->d_tcmin, nt * sizeof(int64_t)));
-  HIPC(hipMalloc(&ctx->d_tcmax, nt * sizeof(int64_t)));
+  HIPC(ctx->d_tcmin.alloc(nt));
+  HIPC(ctx->d_tcmax.alloc(nt));
   CsrDev A;
   A.nrows = ctx->nloc;
   A.rowptr = ctx->d_rowptr;
@@ -1097,7 +1162,7 @@ int prepare_window_formats(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
     f[4] = cmin[t];
     f[5] = cmax[t];
   }
-  HIPC(hipMalloc(&ctx->d_tinfo, 8 * nt * sizeof(int64_t)));
+  HIPC(ctx->d_tinfo.alloc(8 * nt));
   HIPC(hipMemcpy(ctx->d_tinfo, info.data(), 8 * nt * sizeof(int64_t), hipMemcpyHostToDevice));
   const int64_t grid = window_grid();
   ctx->tiles_per_wg = std::max<int64_t>(1, (nt + grid - 1) / grid);
@@ -1109,10 +1174,10 @@ int prepare_window_formats(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
     const double dense_bytes = (double)nt * 16.0 * 16.0 * NG * 8.0;
     if (H && dense_bytes <= 1.25 * 12.0 * (double)ctx->nnz) {
       const size_t elems = (size_t)bt_tile_slots(nt, ctx->tiles_per_wg) * NG * 256;
-      HIPC(hipMalloc(&ctx->d_bt, elems * sizeof(double)));
+      HIPC(ctx->d_bt.alloc(elems));
       HIPC(hipMemsetAsync(ctx->d_bt, 0, elems * sizeof(double), ctx->stream));
       if (!ctx->d_zrow) {
-        HIPC(hipMalloc(&ctx->d_zrow, 64 * sizeof(double)));
+        HIPC(ctx->d_zrow.alloc(64));
         HIPC(hipMemsetAsync(ctx->d_zrow, 0, 64 * sizeof(double), ctx->stream));
       }
       CsrDev A3 = csr(ctx);
@@ -1129,12 +1194,13 @@ int prepare_window_formats(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
       const char* pk = getenv("RBL_BT_PACK");
       if (pk && atoi(pk) == 1) {
         const int64_t nslots = bt_tile_slots(nt, ctx->tiles_per_wg);
-        HIPC(hipMalloc(&ctx->d_btp_hdr, (size_t)nslots * bt_pack_words(NG) * sizeof(uint64_t)));
+        HIPC(ctx->d_btp_hdr.alloc((size_t)nslots * bt_pack_words(NG)));
         int64_t nval = 0;
-        const int prc = bt_pack(ctx->d_bt, nslots, NG, ctx->d_btp_hdr, &ctx->d_btp_val, &nval, ctx->stream);
+        double* pval = nullptr;
+        const int prc = bt_pack(ctx->d_bt, nslots, NG, ctx->d_btp_hdr, &pval, &nval, ctx->stream);
+        ctx->d_btp_val.adopt(pval);
         if (prc != 0) return prc == (int)hipErrorOutOfMemory ? RBL_ERR_OOM : RBL_ERR_HIP;
-        hipFree(ctx->d_bt);
-        ctx->d_bt = nullptr;
+        ctx->d_bt.reset();
       } else {
         // A symmetric (bit for bit, as Lanczos assumes): store the diagonal group and the
         // right strip only — 10 of 18.4 KB per tile at H = 64; the kernel transposes the left
@@ -1146,10 +1212,9 @@ int prepare_window_formats(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
           const int hrc = bt_half(ctx->d_bt, nt, ctx->tiles_per_wg, NG, &half, &edge, ctx->stream);
           if (hrc > 0) return hrc == (int)hipErrorOutOfMemory ? RBL_ERR_OOM : RBL_ERR_HIP;
           if (hrc == 0) {
-            hipFree(ctx->d_bt);
-            ctx->d_bt = nullptr;
-            ctx->d_bth = half;
-            ctx->d_bte = edge;
+            ctx->d_bt.reset();
+            ctx->d_bth.adopt(half);
+            ctx->d_bte.adopt(edge);
           }
         }
       }
@@ -1222,11 +1287,11 @@ int prepare_window_formats(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
     // several-rank setup after this is collective, so no rank may leave before it)
     if (fits) {
       const bool ok =
-          hipMalloc(&ctx->d_panel_val, std::max<int64_t>(ctx->nnz, 1) * sizeof(double)) == hipSuccess &&
-          hipMalloc(&ctx->d_panel_col, std::max<int64_t>(ctx->nnz, 1)) == hipSuccess &&
-          hipMalloc(&ctx->d_panel_blk, 4 * nb * sizeof(int32_t)) == hipSuccess &&
-          hipMalloc(&ctx->d_panel_cnt, std::max<int64_t>(ncnt, 1) * sizeof(uint16_t)) == hipSuccess &&
-          hipMalloc(&ctx->d_panel_st, std::max<int64_t>(ncnt, 1) * sizeof(uint32_t)) == hipSuccess;
+          ctx->d_panel_val.alloc(std::max<int64_t>(ctx->nnz, 1)) == hipSuccess &&
+          ctx->d_panel_col.alloc(std::max<int64_t>(ctx->nnz, 1)) == hipSuccess &&
+          ctx->d_panel_blk.alloc(4 * nb) == hipSuccess &&
+          ctx->d_panel_cnt.alloc(std::max<int64_t>(ncnt, 1)) == hipSuccess &&
+          ctx->d_panel_st.alloc(std::max<int64_t>(ncnt, 1)) == hipSuccess;
       if (!ok) {
         (void)hipGetLastError();
         free_panels(ctx);
@@ -1250,21 +1315,16 @@ int prepare_window_formats(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
       ctx->panel_auto = 4 * staged <= ctx->nnz;
       ctx->panel_span = maxp * pw;
       if (!ctx->d_zrow) {  // the panel rows outside the Q range read it
-        HIPC(hipMalloc(&ctx->d_zrow, 64 * sizeof(double)));
+        HIPC(ctx->d_zrow.alloc(64));
         HIPC(hipMemset(ctx->d_zrow, 0, 64 * sizeof(double)));
       }
     }
   }
   if (!ctx->keep_csr && ctx->bt_ng) {
     // RBL_OPT_KEEP_CSR = 0: the band tiles are the matrix from here on
-    hipFree(ctx->d_col); ctx->d_col = nullptr;
-    hipFree(ctx->d_val); ctx->d_val = nullptr;
-    hipFree(ctx->d_seg_trow); ctx->d_seg_trow = nullptr;
-    hipFree(ctx->d_seg_tinfo); ctx->d_seg_tinfo = nullptr;
-    hipFree(ctx->d_seg_slot_k0); ctx->d_seg_slot_k0 = nullptr;
-    hipFree(ctx->d_seg_lrow); ctx->d_seg_lrow = nullptr;
-    hipFree(ctx->d_seg_lslot); ctx->d_seg_lslot = nullptr;
-    hipFree(ctx->d_seg_scratch); ctx->d_seg_scratch = nullptr;
+    ctx->d_col.reset();
+    ctx->d_val.reset();
+    static_cast<SegTableBufs&>(*ctx) = SegTableBufs{};
     ctx->seg_ntasks = ctx->seg_nlong = 0;
     free_tiers(ctx);
     ctx->window_ok16 = ctx->window_ok32 = false;
@@ -1274,7 +1334,7 @@ int prepare_window_formats(rbl_ctx* ctx, const std::vector<int64_t>& rp) {
     return RBL_OK;
   }
   if (ctx->band_ok16 || ctx->band_ok32) {  // dense-tile positions for the band kernel
-    HIPC(hipMalloc(&ctx->d_bpos, (ctx->nnz + kCsrPad) * sizeof(uint16_t)));
+    HIPC(ctx->d_bpos.alloc(ctx->nnz + kCsrPad));
     HIPC(hipMemsetAsync(ctx->d_bpos + ctx->nnz, 0, kCsrPad * sizeof(uint16_t), ctx->stream));
     CsrDev A2 = csr(ctx);
     band_positions(A2, ctx->d_bpos, ctx->stream);
@@ -1541,21 +1601,19 @@ CsrDev::Tier rect_tier(const rbl_ctx* ctx, int side) {
 int ensure_rect_y(rbl_ctx* ctx, int b) {
   if (!ctx->d_rect_y || ctx->rect_y_cols < b) {
     HIPC(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->d_rect_y);
-    ctx->d_rect_y = nullptr;
+    ctx->d_rect_y.reset();
     ctx->rect_y_cols = 0;
-    HIPC(hipMalloc(&ctx->d_rect_y, (size_t)ctx->rect_m * b * sizeof(double)));
+    HIPC(ctx->d_rect_y.alloc((size_t)ctx->rect_m * b));
     ctx->rect_y_cols = b;
   }
   if (ctx->rect_shift && ctx->rect_ts_cols < b) {
     HIPC(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->d_rect_ts);
-    hipFree(ctx->d_rect_part);
-    ctx->d_rect_ts = ctx->d_rect_part = nullptr;
+    ctx->d_rect_ts.reset();
+    ctx->d_rect_part.reset();
     ctx->rect_ts_cols = 0;
     const size_t grid = (size_t)rect_colsum_grid(std::max(ctx->rect_m, ctx->n), b);
-    HIPC(hipMalloc(&ctx->d_rect_ts, (size_t)2 * b * sizeof(double)));
-    HIPC(hipMalloc(&ctx->d_rect_part, grid * b * sizeof(double)));
+    HIPC(ctx->d_rect_ts.alloc((size_t)2 * b));
+    HIPC(ctx->d_rect_part.alloc(grid * b));
     ctx->rect_ts_cols = b;
   }
   return RBL_OK;
@@ -1570,7 +1628,7 @@ bool direct32_ok(const rbl_ctx* ctx, int b) {
 // allocated on first use when the direct path made it unnecessary at rbl_start
 int ensure_qm64(rbl_ctx* ctx) {
   if (ctx->d_Qm64) return RBL_OK;
-  HIPC(hipMalloc(&ctx->d_Qm64, (std::max<int64_t>(ctx->nloc, 1) + kRowPad) * ctx->b * sizeof(double)));
+  HIPC(ctx->d_Qm64.alloc((std::max<int64_t>(ctx->nloc, 1) + kRowPad) * ctx->b));
   return RBL_OK;
 }
 
@@ -1591,10 +1649,9 @@ int ensure_qext(rbl_ctx* ctx, int b, hipStream_t st) {
   const size_t need = (size_t)qext_rows(ctx, b) * b;
   if (ctx->d_qext && ctx->qext_cap >= need) return RBL_OK;
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(ctx->d_qext);
-  ctx->d_qext = nullptr;
+  ctx->d_qext.reset();
   ctx->qext_cap = 0;
-  HIPC(hipMalloc(&ctx->d_qext, need * sizeof(double)));
+  HIPC(ctx->d_qext.alloc(need));
   HIPC(hipMemsetAsync(ctx->d_qext, 0, need * sizeof(double), st));
   ctx->qext_cap = need;
   return RBL_OK;
@@ -1666,10 +1723,9 @@ int apply_A_stored(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* 
     return parts;
   }
   if (b > ctx->qfull_cols) {  // Q gathered to all n rows, zero-padded to 32 * dense_panels
-    hipFree(ctx->d_qfull);
-    ctx->d_qfull = nullptr;
+    ctx->d_qfull.reset();
     ctx->qfull_cols = 0;
-    HIPC(hipMalloc(&ctx->d_qfull, (size_t)ctx->dense_panels * 32 * b * sizeof(double)));
+    HIPC(ctx->d_qfull.alloc((size_t)ctx->dense_panels * 32 * b));
     HIPC(hipMemsetAsync(ctx->d_qfull, 0, (size_t)ctx->dense_panels * 32 * b * sizeof(double), ctx->stream));
     ctx->qfull_cols = b;
   }
@@ -1693,13 +1749,12 @@ int apply_A_stored(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* 
 int ensure_lr_bufs(rbl_ctx* ctx, int b) {
   if (ctx->d_lr_wc && ctx->lr_cols >= b) return RBL_OK;
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(ctx->d_lr_wc);
-  hipFree(ctx->d_lr_part);
-  ctx->d_lr_wc = ctx->d_lr_part = nullptr;
+  ctx->d_lr_wc.reset();
+  ctx->d_lr_part.reset();
   ctx->lr_cols = 0;
   const size_t grid = (size_t)lr_project_grid(ctx->nloc, b, ctx->lr_rp);
-  HIPC(hipMalloc(&ctx->d_lr_wc, (size_t)2 * ctx->lr_rp * b * sizeof(double)));
-  HIPC(hipMalloc(&ctx->d_lr_part, grid * ctx->lr_rp * b * sizeof(double)));
+  HIPC(ctx->d_lr_wc.alloc((size_t)2 * ctx->lr_rp * b));
+  HIPC(ctx->d_lr_part.alloc(grid * ctx->lr_rp * b));
   ctx->lr_cols = b;
   return RBL_OK;
 }
@@ -1745,22 +1800,18 @@ int ensure_filter_bufs(rbl_ctx* ctx, int b) {
   if (ctx->d_filt[0] && ctx->d_filt[1] && ctx->filt_cols >= b) {
     if (want == 2 || ctx->d_filt[2]) return RBL_OK;
     // the two blocks of an earlier filter stay; the series' third joins them at their width
-    const size_t bytes =
-        (size_t)(std::max<int64_t>(ctx->nloc, 1) + kRowPad) * ctx->filt_cols * sizeof(double);
-    HIPC(hipMalloc(&ctx->d_filt[2], bytes));
-    HIPC(hipMemsetAsync(ctx->d_filt[2], 0, bytes, ctx->stream));
+    const size_t len = (size_t)(std::max<int64_t>(ctx->nloc, 1) + kRowPad) * ctx->filt_cols;
+    HIPC(ctx->d_filt[2].alloc(len));
+    HIPC(hipMemsetAsync(ctx->d_filt[2], 0, len * sizeof(double), ctx->stream));
     return RBL_OK;
   }
   HIPC(hipStreamSynchronize(ctx->stream));
-  const size_t bytes = (size_t)(std::max<int64_t>(ctx->nloc, 1) + kRowPad) * b * sizeof(double);
-  for (double*& p : ctx->d_filt) {
-    hipFree(p);
-    p = nullptr;
-  }
+  const size_t len = (size_t)(std::max<int64_t>(ctx->nloc, 1) + kRowPad) * b;
+  for (auto& p : ctx->d_filt) p.reset();
   ctx->filt_cols = 0;
   for (int q = 0; q < want; ++q) {
-    HIPC(hipMalloc(&ctx->d_filt[q], bytes));
-    HIPC(hipMemsetAsync(ctx->d_filt[q], 0, bytes, ctx->stream));
+    HIPC(ctx->d_filt[q].alloc(len));
+    HIPC(hipMemsetAsync(ctx->d_filt[q], 0, len * sizeof(double), ctx->stream));
   }
   ctx->filt_cols = b;
   return RBL_OK;
@@ -1815,7 +1866,7 @@ int cheb_apply(rbl_ctx* ctx, const double* X, int b, double* out, double* F0, do
 // term 1 and T_{j-2} of term 2.  T_j lives in F[j % 3]: term j's SpMM writes W = A T_{j-1} into
 // the block that held T_{j-3} (dead by then) and the fused pass turns W into T_j in place while
 // it adds mu_j T_j to out; the first pass initialises out, the last stores no T_d.
-int series_apply(rbl_ctx* ctx, const double* X, int b, double* out, double* const F[3]) {
+int series_apply(rbl_ctx* ctx, const double* X, int b, double* out, const DevBuf<double> F[3]) {
   if (ctx->nloc <= 0) return RBL_OK;
   const std::vector<double>& mu = ctx->ser_mu;
   const int d = (int)mu.size() - 1;
@@ -1837,7 +1888,7 @@ int series_apply(rbl_ctx* ctx, const double* X, int b, double* out, double* cons
 }
 
 // out = p(A) X with whichever filter is set (has_filter; the work blocks from ensure_filter_bufs)
-int filter_apply(rbl_ctx* ctx, const double* X, int b, double* out, double* const F[3]) {
+int filter_apply(rbl_ctx* ctx, const double* X, int b, double* out, const DevBuf<double> F[3]) {
   if (has_series(ctx)) return series_apply(ctx, X, b, out, F);
   return cheb_apply(ctx, X, b, out, F[0], F[1]);
 }
@@ -1955,15 +2006,13 @@ int combine_blocks(rbl_ctx* ctx, int nblocks, int kcols, const double* d_S, doub
 int basis_combine(rbl_ctx* ctx, int nblocks, int kcols, const double* S, double* Y) {
   const int b = ctx->b;
   const int64_t rows = (int64_t)nblocks * b;
-  double *d_Scm = nullptr, *d_S = nullptr;
-  HIPC(hipMalloc(&d_Scm, rows * kcols * sizeof(double)));
-  HIPC(hipMalloc(&d_S, rows * kcols * sizeof(double)));
+  DevBuf<double> d_Scm, d_S;
+  HIPC(d_Scm.alloc(rows * kcols));
+  HIPC(d_S.alloc(rows * kcols));
   HIPC(hipMemcpyAsync(d_Scm, S, rows * kcols * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   colmajor_to_rowmajor(d_Scm, rows, kcols, d_S, ctx->stream);
   const int st = combine_blocks(ctx, nblocks, kcols, d_S, Y);
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(d_S);
-  hipFree(d_Scm);
   return st;
 }
 
@@ -2238,7 +2287,7 @@ int halo_exchange32(rbl_ctx* ctx, const float* Q, const float** Qin, int64_t* of
   }
   StageScope t(ctx, RBL_STAGE_COMM);
   const int b = ctx->b;
-  float* ext = reinterpret_cast<float*>(ctx->d_qext);
+  float* ext = reinterpret_cast<float*>(ctx->d_qext.p);
   if (copy_local)
     HIPC(hipMemcpyAsync(ext + (ctx->r0 - ctx->ext_lo) * b, Q, ctx->nloc * b * sizeof(float),
                         hipMemcpyDeviceToDevice, ctx->stream));
@@ -2274,6 +2323,16 @@ constexpr bool ritz_serial() { return false; }
 
 // one step's record in the async stash: A_i, R_tot (b x b each) and 4 int flags (2 doubles)
 size_t stash_rec(int b) { return (size_t)2 * b * b + 2; }
+
+// the side stream of the host spill (D2H copies of finished blocks) and its events
+int ensure_spill_stream(rbl_ctx* ctx) {
+  if (ctx->cstream) return RBL_OK;
+  HIPC(hipStreamCreateWithFlags(&ctx->cstream, hipStreamNonBlocking));
+  HIPC(hipEventCreateWithFlags(&ctx->ev_fin, hipEventDisableTiming));
+  HIPC(hipEventCreateWithFlags(&ctx->ev_d2h[0], hipEventDisableTiming));
+  HIPC(hipEventCreateWithFlags(&ctx->ev_d2h[1], hipEventDisableTiming));
+  return RBL_OK;
+}
 // The staged D2H of the Ritz vectors (d2h_staged): two pinned 64 MiB slots and their events,
 // kept for the context's life.  Pinning them costs ~20-30 ms, so rbl_start allocates them with
 // the run's buffers when a Ritz result will take the staged path (one basis block >= 256 MiB),
@@ -2281,7 +2340,7 @@ size_t stash_rec(int b) { return (size_t)2 * b * b + 2; }
 constexpr size_t kD2HPiece = size_t(64) << 20;
 int ensure_d2h_slots(rbl_ctx* ctx) {
   for (int s = 0; s < 2; ++s) {
-    if (!ctx->h_d2h[s]) HIPC(hipHostMalloc(&ctx->h_d2h[s], kD2HPiece, hipHostMallocDefault));
+    if (!ctx->h_d2h[s]) HIPC(ctx->h_d2h[s].alloc(kD2HPiece, hipHostMallocDefault));
     if (!ctx->ev_d2h_slot[s]) HIPC(hipEventCreateWithFlags(&ctx->ev_d2h_slot[s], hipEventDisableTiming));
   }
   return RBL_OK;
@@ -2311,11 +2370,11 @@ int ensure_push(rbl_ctx* ctx, int b) {
   if (ctx->d_pushbuf && ctx->push_cap >= need) return RBL_OK;
   HIPC(hipStreamSynchronize(ctx->stream));
   if (ctx->hstream) HIPC(hipStreamSynchronize(ctx->hstream));
-  hipFree(ctx->d_pushbuf); ctx->d_pushbuf = nullptr;
-  hipFree(ctx->d_precv); ctx->d_precv = nullptr;
+  ctx->d_pushbuf.reset();
+  ctx->d_precv.reset();
   ctx->push_cap = 0;
-  HIPC(hipMalloc(&ctx->d_pushbuf, need * sizeof(double)));
-  HIPC(hipMalloc(&ctx->d_precv, need * sizeof(double)));
+  HIPC(ctx->d_pushbuf.alloc(need));
+  HIPC(ctx->d_precv.alloc(need));
   ctx->push_cap = need;
   return RBL_OK;
 }
@@ -2374,49 +2433,20 @@ int push_halo(rbl_ctx* ctx, const double* Q, int b, double* U) {
 }
 
 void free_run(rbl_ctx* ctx) {
+  // the side streams first: the spill copies read the basis, the halo stream the push buffers
   if (ctx->cstream) hipStreamSynchronize(ctx->cstream);
-  hipFree(ctx->d_basis); ctx->d_basis = nullptr;
-  for (void* h : ctx->h_spill)
-    if (h) hipHostFree(h);
-  ctx->h_spill.clear();
-  hipFree(ctx->d_stage); ctx->d_stage = nullptr;
+  if (ctx->hstream) hipStreamSynchronize(ctx->hstream);
+  static_cast<RunBufs&>(*ctx) = RunBufs{};
   ctx->resident = INT32_MAX;
   ctx->d2h_pending[0] = ctx->d2h_pending[1] = false;
-  hipFree(ctx->d_basis32); ctx->d_basis32 = nullptr;
-  hipFree(ctx->d_stage32); ctx->d_stage32 = nullptr;
-  hipFree(ctx->d_Qi64); ctx->d_Qi64 = nullptr;
-  hipFree(ctx->d_Qm64); ctx->d_Qm64 = nullptr;
   ctx->basis_bits = 64;
-  hipFree(ctx->d_U); ctx->d_U = nullptr;
-  hipFree(ctx->d_T); ctx->d_T = nullptr;
-  hipFree(ctx->d_qext); ctx->d_qext = nullptr; ctx->qext_cap = 0;
-  hipFree(ctx->d_sendbuf); ctx->d_sendbuf = nullptr;
-  if (ctx->hstream) hipStreamSynchronize(ctx->hstream);
-  hipFree(ctx->d_pushbuf); ctx->d_pushbuf = nullptr;
-  hipFree(ctx->d_precv); ctx->d_precv = nullptr;
+  ctx->qext_cap = 0;
   ctx->push_cap = 0;
-  hipFree(ctx->d_slab); ctx->d_slab = nullptr;
-  hipFree(ctx->d_C); ctx->d_C = nullptr;
-  hipFree(ctx->d_small); ctx->d_small = nullptr;
-  hipFree(ctx->d_flags); ctx->d_flags = nullptr;
-  hipFree(ctx->d_lock); ctx->d_lock = nullptr;
   ctx->nlock = ctx->lock_cap = 0;
-  hipFree(ctx->d_arrow_W); ctx->d_arrow_W = nullptr;
-  hipFree(ctx->d_tr_S); ctx->d_tr_S = nullptr;
   ctx->arrow_W_cap = ctx->tr_S_cap = 0;
   ctx->arrow_kb = 0;
-  hipFree(ctx->d_filt[0]); hipFree(ctx->d_filt[1]); hipFree(ctx->d_filt[2]);
-  ctx->d_filt[0] = ctx->d_filt[1] = ctx->d_filt[2] = nullptr;
   ctx->filt_cols = 0;
-  hipFree(ctx->d_rv); ctx->d_rv = nullptr;
-  hipFree(ctx->d_rw); ctx->d_rw = nullptr;
   ctx->ritz_k = 0;
-  if (ctx->h_pin) hipHostFree(ctx->h_pin);
-  ctx->h_pin = nullptr;
-  if (ctx->h_hist) hipHostFree(ctx->h_hist);
-  ctx->h_hist = nullptr;
-  hipFree(ctx->d_stash);
-  ctx->d_stash = nullptr;
   ctx->dv_pin = ctx->dv_hist = nullptr;
   ctx->nblocks = 0;
   ctx->b = 0;
@@ -2425,57 +2455,32 @@ void free_run(rbl_ctx* ctx) {
 
 // the rank-one shift of a rectangular B and the buffers of its reductions
 void free_rect_shift(rbl_ctx* ctx) {
-  hipFree(ctx->d_shift_u); ctx->d_shift_u = nullptr;
-  hipFree(ctx->d_shift_v); ctx->d_shift_v = nullptr;
-  hipFree(ctx->d_rect_ts); ctx->d_rect_ts = nullptr;
-  hipFree(ctx->d_rect_part); ctx->d_rect_part = nullptr;
+  static_cast<RectShiftBufs&>(*ctx) = RectShiftBufs{};
   ctx->rect_ts_cols = 0;
   ctx->rect_shift = false;
 }
 
 // the low-rank update and the buffers of its passes
 void free_lowrank(rbl_ctx* ctx) {
-  hipFree(ctx->d_lr_P); ctx->d_lr_P = nullptr;
-  hipFree(ctx->d_lr_S); ctx->d_lr_S = nullptr;
-  hipFree(ctx->d_lr_wc); ctx->d_lr_wc = nullptr;
-  hipFree(ctx->d_lr_part); ctx->d_lr_part = nullptr;
+  static_cast<LowrankBufs&>(*ctx) = LowrankBufs{};
   ctx->lr_cols = 0;
   ctx->lr_r = ctx->lr_rp = 0;
 }
 
 void free_matrix(rbl_ctx* ctx) {
-  hipFree(ctx->d_rowptr); ctx->d_rowptr = nullptr;
-  hipFree(ctx->d_col); ctx->d_col = nullptr;
-  hipFree(ctx->d_val); ctx->d_val = nullptr;
-  hipFree(ctx->d_tcmin); ctx->d_tcmin = nullptr;
-  hipFree(ctx->d_tcmax); ctx->d_tcmax = nullptr;
-  hipFree(ctx->d_tinfo); ctx->d_tinfo = nullptr;
+  // the parts that are also released alone reset their own scalars; then every matrix buffer
   free_panels(ctx);
-  hipFree(ctx->d_bpos); ctx->d_bpos = nullptr;
-  hipFree(ctx->d_bt); ctx->d_bt = nullptr;
-  hipFree(ctx->d_bth); ctx->d_bth = nullptr;
-  hipFree(ctx->d_bte); ctx->d_bte = nullptr;
-  hipFree(ctx->d_btp_hdr); ctx->d_btp_hdr = nullptr;
-  hipFree(ctx->d_btp_val); ctx->d_btp_val = nullptr;
-  hipFree(ctx->d_zrow); ctx->d_zrow = nullptr;
-  ctx->bt_ng = 0;
-  hipFree(ctx->d_seg_trow); ctx->d_seg_trow = nullptr;
-  hipFree(ctx->d_seg_tinfo); ctx->d_seg_tinfo = nullptr;
-  hipFree(ctx->d_seg_slot_k0); ctx->d_seg_slot_k0 = nullptr;
-  hipFree(ctx->d_seg_lrow); ctx->d_seg_lrow = nullptr;
-  hipFree(ctx->d_seg_lslot); ctx->d_seg_lslot = nullptr;
-  hipFree(ctx->d_seg_scratch); ctx->d_seg_scratch = nullptr;
-  ctx->seg_ntasks = ctx->seg_nlong = 0;
   free_tiers(ctx);
-  for (auto& T : ctx->rect_side) free_seg(T, true);
-  hipFree(ctx->d_rect_y); ctx->d_rect_y = nullptr; ctx->rect_y_cols = 0;
   free_rect_shift(ctx);
   free_lowrank(ctx);
+  static_cast<MatrixBufs&>(*ctx) = MatrixBufs{};
+  ctx->bt_ng = 0;
+  ctx->seg_ntasks = ctx->seg_nlong = 0;
+  ctx->rect_y_cols = 0;
   ctx->arrow_kb = 0;  // a pending arrow step belongs to the operator its basis was built with
   ctx->rect = false;
   ctx->rect_m = 0;
-  hipFree(ctx->d_dense); ctx->d_dense = nullptr;
-  hipFree(ctx->d_qfull); ctx->d_qfull = nullptr; ctx->qfull_cols = 0;
+  ctx->qfull_cols = 0;
   ctx->dense = false;
   ctx->dense_panels = 0;
   ctx->n = ctx->nloc = ctx->nnz = 0;
@@ -2515,6 +2520,35 @@ int setup_halo(rbl_ctx* ctx) {
   return RBL_OK;
 }
 
+// The CSR arrays of m rows and nnz nonzeros, the kCsrPad entries past the last zeroed.
+int alloc_csr(rbl_ctx* ctx, int64_t m, int64_t nnz) {
+  HIPC(ctx->d_rowptr.alloc(m + 1));
+  HIPC(ctx->d_col.alloc(nnz + kCsrPad));
+  HIPC(ctx->d_val.alloc(nnz + kCsrPad));
+  HIPC(hipMemset(ctx->d_col + nnz, 0, kCsrPad * sizeof(int32_t)));
+  HIPC(hipMemset(ctx->d_val + nnz, 0, kCsrPad * sizeof(double)));
+  return RBL_OK;
+}
+
+// A generator's planted eigenvalues on the device (none: d_plant stays null).
+int upload_plant(rbl_ctx* ctx, int nplant, const double* plant, DevBuf<double>& d_plant) {
+  if (nplant <= 0) return RBL_OK;
+  HIPC(d_plant.alloc(nplant));
+  HIPC(hipMemcpy(d_plant, plant, nplant * sizeof(double), hipMemcpyHostToDevice));
+  return RBL_OK;
+}
+
+// A generator's per-row counts (device, m int32) as the row pointer rp; sets ctx->nnz.
+int counts_to_rowptr(rbl_ctx* ctx, const int32_t* d_cnt, int64_t m, std::vector<int64_t>& rp) {
+  std::vector<int32_t> cnt(m);
+  HIPC(hipMemcpyAsync(cnt.data(), d_cnt, m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  rp.assign(m + 1, 0);
+  for (int64_t i = 0; i < m; ++i) rp[i + 1] = rp[i] + cnt[i];
+  ctx->nnz = rp[m];
+  return RBL_OK;
+}
+
 // Upload a local CSR (0-based rowptr relative to the slice, global 0-based int64 columns).
 int upload_csr(rbl_ctx* ctx, int64_t n, int64_t r0, int64_t r1, const int64_t* rowptr,
                const int64_t* colind, const double* val, int64_t base_ptr, int64_t base_idx) {
@@ -2541,11 +2575,7 @@ int upload_csr(rbl_ctx* ctx, int64_t n, int64_t r0, int64_t r1, const int64_t* r
   ctx->r1 = r1;
   ctx->nloc = m;
   ctx->nnz = nnz;
-  HIPC(hipMalloc(&ctx->d_rowptr, (m + 1) * sizeof(int64_t)));
-  HIPC(hipMalloc(&ctx->d_col, (nnz + kCsrPad) * sizeof(int32_t)));
-  HIPC(hipMalloc(&ctx->d_val, (nnz + kCsrPad) * sizeof(double)));
-  HIPC(hipMemset(ctx->d_col + nnz, 0, kCsrPad * sizeof(int32_t)));
-  HIPC(hipMemset(ctx->d_val + nnz, 0, kCsrPad * sizeof(double)));
+  CHK(alloc_csr(ctx, m, nnz));
   HIPC(hipMemcpy(ctx->d_rowptr, rp.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   if (nnz) {
     HIPC(hipMemcpy(ctx->d_col, ci.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -2582,10 +2612,10 @@ int halo_from_footprint(rbl_ctx* ctx) {
   ctx->need_lo.assign(P, 0);
   ctx->need_hi.assign(P, 0);
   if (P > 1 && nnz > 0) {
-    int64_t* d_b = nullptr;
-    unsigned long long* d_lh = nullptr;
-    HIPC(hipMalloc(&d_b, (P + 1) * sizeof(int64_t)));
-    HIPC(hipMalloc(&d_lh, 2 * P * sizeof(unsigned long long)));
+    DevBuf<int64_t> d_b;
+    DevBuf<unsigned long long> d_lh;
+    HIPC(d_b.alloc(P + 1));
+    HIPC(d_lh.alloc(2 * P));
     std::vector<unsigned long long> lh(2 * P);
     for (int q = 0; q < P; ++q) { lh[q] = ~0ull; lh[P + q] = 0ull; }
     HIPC(hipMemcpy(d_b, ctx->bounds.data(), (P + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -2594,8 +2624,6 @@ int halo_from_footprint(rbl_ctx* ctx) {
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(lh.data(), d_lh, 2 * P * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
-    hipFree(d_b);
-    hipFree(d_lh);
     for (int q = 0; q < P; ++q) {
       if (q == ctx->rank || lh[P + q] == 0ull) continue;
       ctx->need_lo[q] = (int64_t)lh[q];
@@ -2648,12 +2676,12 @@ int rbl_comm_selftest(int device, char* msg, int msg_len) {
   Comm* c = make_rccl_comm(1, 0, id, &err);
   if (!c) { say("ncclCommInitRank: " + err); return RBL_ERR_RCCL; }
   hipStream_t st = nullptr;
-  double* d = nullptr;
+  DevBuf<double> d;
   int rc = RBL_OK;
   const size_t n = 4096;
   std::vector<double> h(n), back(n);
   for (size_t k = 0; k < n; ++k) h[k] = 0.5 * (double)k - 7.0;
-  if (hipStreamCreate(&st) != hipSuccess || hipMalloc(&d, 2 * n * sizeof(double)) != hipSuccess ||
+  if (hipStreamCreate(&st) != hipSuccess || d.alloc(2 * n) != hipSuccess ||
       hipMemcpy(d, h.data(), n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
     say("HIP setup failed");
     rc = RBL_ERR_HIP;
@@ -2675,7 +2703,7 @@ int rbl_comm_selftest(int device, char* msg, int msg_len) {
   if (rc == RBL_OK && hipStreamSynchronize(st) != hipSuccess) { say("stream sync failed"); rc = RBL_ERR_HIP; }
   if (rc == RBL_OK) say(std::string("ok: ") + c->name());
   delete c;
-  if (d) (void)hipFree(d);
+  d.reset();
   if (st) (void)hipStreamDestroy(st);
   return rc;
 }
@@ -2754,8 +2782,7 @@ int rbl_free(rbl_ctx* ctx) {
   for (hipEvent_t e : {ctx->ev_fin, ctx->ev_d2h[0], ctx->ev_d2h[1], ctx->ev_d2h_slot[0],
                        ctx->ev_d2h_slot[1], ctx->ev_qready, ctx->ev_halo})
     if (e) hipEventDestroy(e);
-  for (void* h : ctx->h_d2h)
-    if (h) hipHostFree(h);
+  static_cast<CtxBufs&>(*ctx) = CtxBufs{};
   delete ctx;
   return RBL_OK;
 }
@@ -2915,13 +2942,13 @@ int rbl_set_matrix_dense(rbl_ctx* ctx, int64_t n, int64_t row_begin, int64_t row
   ctx->dense_panels = (n + 31) / 32;
   const int64_t P = ctx->dense_panels;
   const int64_t ml = std::max<int64_t>(m, 1);
-  HIPC(hipMalloc(&ctx->d_dense, (size_t)P * ml * 32 * sizeof(double)));
-  HIPC(hipMalloc(&ctx->d_qfull, (size_t)P * 32 * 64 * sizeof(double)));
+  HIPC(ctx->d_dense.alloc((size_t)P * ml * 32));
+  HIPC(ctx->d_qfull.alloc((size_t)P * 32 * 64));
   HIPC(hipMemsetAsync(ctx->d_qfull, 0, (size_t)P * 32 * 64 * sizeof(double), ctx->stream));
   ctx->qfull_cols = 64;
   // column-major slice -> row-major 32-column panels, one panel at a time through a scratch
-  double* d_tmp = nullptr;
-  HIPC(hipMalloc(&d_tmp, (size_t)ml * 32 * sizeof(double)));
+  DevBuf<double> d_tmp;
+  HIPC(d_tmp.alloc((size_t)ml * 32));
   for (int64_t p = 0; p < P && m > 0; ++p) {
     const int64_t c0 = 32 * p, nc = std::min<int64_t>(32, n - c0);
     if (nc < 32) HIPC(hipMemsetAsync(d_tmp, 0, (size_t)m * 32 * sizeof(double), ctx->stream));
@@ -2931,7 +2958,7 @@ int rbl_set_matrix_dense(rbl_ctx* ctx, int64_t n, int64_t row_begin, int64_t row
   }
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(d_tmp);
+  d_tmp.reset();
   // every rank needs all n rows of Q
   const int Pr = ctx->nranks;
   ctx->need_lo.assign(Pr, 0);
@@ -2958,32 +2985,21 @@ int rbl_gen_matrix_hashwindow(rbl_ctx* ctx, int64_t n, int64_t halfwidth, double
   ctx->r0 = r0;
   ctx->r1 = r1;
   ctx->nloc = m;
-  int32_t* d_cnt = nullptr;
-  HIPC(hipMalloc(&d_cnt, std::max<int64_t>(m, 1) * sizeof(int32_t)));
+  DevBuf<int32_t> d_cnt;
+  HIPC(d_cnt.alloc(std::max<int64_t>(m, 1)));
   hw_count(n, halfwidth, density, seed, r0, r1, d_cnt, ctx->stream);
-  std::vector<int32_t> cnt(m);
-  HIPC(hipMemcpyAsync(cnt.data(), d_cnt, m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(d_cnt);
-  std::vector<int64_t> rp(m + 1, 0);
-  for (int64_t i = 0; i < m; ++i) rp[i + 1] = rp[i] + cnt[i];
-  ctx->nnz = rp[m];
-  HIPC(hipMalloc(&ctx->d_rowptr, (m + 1) * sizeof(int64_t)));
-  HIPC(hipMalloc(&ctx->d_col, (ctx->nnz + kCsrPad) * sizeof(int32_t)));
-  HIPC(hipMalloc(&ctx->d_val, (ctx->nnz + kCsrPad) * sizeof(double)));
-  HIPC(hipMemset(ctx->d_col + ctx->nnz, 0, kCsrPad * sizeof(int32_t)));
-  HIPC(hipMemset(ctx->d_val + ctx->nnz, 0, kCsrPad * sizeof(double)));
+  std::vector<int64_t> rp;
+  CHK(counts_to_rowptr(ctx, d_cnt, m, rp));
+  d_cnt.reset();  // m counts, before the CSR
+  CHK(alloc_csr(ctx, m, ctx->nnz));
   HIPC(hipMemcpy(ctx->d_rowptr, rp.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  double* d_plant = nullptr;
-  if (nplant > 0) {
-    HIPC(hipMalloc(&d_plant, nplant * sizeof(double)));
-    HIPC(hipMemcpy(d_plant, plant, nplant * sizeof(double), hipMemcpyHostToDevice));
-  }
+  DevBuf<double> d_plant;
+  CHK(upload_plant(ctx, nplant, plant, d_plant));
   hw_fill(n, halfwidth, density, seed, r0, r1, ctx->d_rowptr, nplant, d_plant, ctx->d_col,
           ctx->d_val, ctx->stream);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(d_plant);
+  d_plant.reset();  // before the formats are built, so their allocations are placed as ever
   ctx->need_lo.assign(P, 0);
   ctx->need_hi.assign(P, 0);
   for (int q = 0; q < P; ++q) {  // analytic footprint of the window
@@ -3014,33 +3030,22 @@ int rbl_gen_matrix_circuit(rbl_ctx* ctx, int64_t n, int64_t width, double p_edge
   ctx->r0 = r0;
   ctx->r1 = r1;
   ctx->nloc = m;
-  int32_t* d_cnt = nullptr;
-  HIPC(hipMalloc(&d_cnt, std::max<int64_t>(m, 1) * sizeof(int32_t)));
+  DevBuf<int32_t> d_cnt;
+  HIPC(d_cnt.alloc(std::max<int64_t>(m, 1)));
   circ_count(n, width, p_edge, seed, r0, r1, d_cnt, ctx->stream);
   HIPC(hipGetLastError());
-  std::vector<int32_t> cnt(m);
-  HIPC(hipMemcpyAsync(cnt.data(), d_cnt, m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(d_cnt);
-  std::vector<int64_t> rp(m + 1, 0);
-  for (int64_t i = 0; i < m; ++i) rp[i + 1] = rp[i] + cnt[i];
-  ctx->nnz = rp[m];
-  HIPC(hipMalloc(&ctx->d_rowptr, (m + 1) * sizeof(int64_t)));
-  HIPC(hipMalloc(&ctx->d_col, (ctx->nnz + kCsrPad) * sizeof(int32_t)));
-  HIPC(hipMalloc(&ctx->d_val, (ctx->nnz + kCsrPad) * sizeof(double)));
-  HIPC(hipMemset(ctx->d_col + ctx->nnz, 0, kCsrPad * sizeof(int32_t)));
-  HIPC(hipMemset(ctx->d_val + ctx->nnz, 0, kCsrPad * sizeof(double)));
+  std::vector<int64_t> rp;
+  CHK(counts_to_rowptr(ctx, d_cnt, m, rp));
+  d_cnt.reset();  // m counts, before the CSR
+  CHK(alloc_csr(ctx, m, ctx->nnz));
   HIPC(hipMemcpy(ctx->d_rowptr, rp.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  double* d_plant = nullptr;
-  if (nplant > 0) {
-    HIPC(hipMalloc(&d_plant, nplant * sizeof(double)));
-    HIPC(hipMemcpy(d_plant, plant, nplant * sizeof(double), hipMemcpyHostToDevice));
-  }
+  DevBuf<double> d_plant;
+  CHK(upload_plant(ctx, nplant, plant, d_plant));
   circ_fill(n, width, p_edge, seed, r0, r1, ctx->d_rowptr, nplant, d_plant, ctx->d_col,
             ctx->d_val, ctx->stream);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(d_plant);
+  d_plant.reset();  // before the formats are built, so their allocations are placed as ever
   CHK(halo_from_footprint(ctx));
   CHK(prepare_window(ctx, rp));
   return setup_halo(ctx);
@@ -3068,15 +3073,15 @@ int rbl_gen_matrix_rmat(rbl_ctx* ctx, int64_t n, int scale, int64_t edges, doubl
   if (p.relabel) p.perm = make_scatter(n, seed ^ kRelabelK);
   // degrees of every row (all ranks draw every edge): they size the key buffer and balance
   // the row split by nonzeros (R-MAT's low ids are its hubs)
-  int32_t* d_deg = nullptr;
-  HIPC(hipMalloc(&d_deg, n * sizeof(int32_t)));
+  DevBuf<int32_t> d_deg;
+  HIPC(d_deg.alloc(n));
   HIPC(hipMemsetAsync(d_deg, 0, n * sizeof(int32_t), ctx->stream));
   rmat_degree(p, d_deg, ctx->stream);
   HIPC(hipGetLastError());
   std::vector<int32_t> deg(n);
   HIPC(hipMemcpyAsync(deg.data(), d_deg, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(d_deg);
+  d_deg.reset();  // n degrees, before the CSR
   const int P = ctx->nranks;
   std::vector<int64_t> pre(n + 1, 0);  // nonzeros (with duplicates) + diagonal, prefix
   for (int64_t r = 0; r < n; ++r) pre[r + 1] = pre[r] + deg[r] + 1;
@@ -3094,16 +3099,17 @@ int rbl_gen_matrix_rmat(rbl_ctx* ctx, int64_t n, int scale, int64_t edges, doubl
   ctx->nloc = m;
   int64_t own = 0;
   for (int64_t r = r0; r < r1; ++r) own += deg[r];
-  double* d_plant = nullptr;
-  if (nplant > 0) {
-    HIPC(hipMalloc(&d_plant, nplant * sizeof(double)));
-    HIPC(hipMemcpy(d_plant, plant, nplant * sizeof(double), hipMemcpyHostToDevice));
-  }
-  HIPC(hipMalloc(&ctx->d_rowptr, (m + 1) * sizeof(int64_t)));
+  DevBuf<double> d_plant;
+  CHK(upload_plant(ctx, nplant, plant, d_plant));
+  HIPC(ctx->d_rowptr.alloc(m + 1));
   int64_t nnz = 0;
-  const int st = rmat_local_csr(p, r0, r1, own, nplant, d_plant, ctx->d_rowptr, &ctx->d_col,
-                                &ctx->d_val, &nnz, ctx->stream);
-  hipFree(d_plant);
+  int32_t* col = nullptr;  // the generator allocates both: adopted whatever it returns
+  double* val = nullptr;
+  const int st = rmat_local_csr(p, r0, r1, own, nplant, d_plant, ctx->d_rowptr, &col, &val, &nnz,
+                                ctx->stream);
+  ctx->d_col.adopt(col);
+  ctx->d_val.adopt(val);
+  d_plant.reset();  // before the formats are built, so their allocations are placed as ever
   ctx->relabeled = p.relabel;
   ctx->relabel_perm = p.perm;
   if (st == -1) return fail(ctx, RBL_ERR_INVALID, "rbl_gen_matrix_rmat: > 2^31 keys on one rank");
@@ -3164,12 +3170,12 @@ int rbl_set_matrix_normal(rbl_ctx* ctx, int64_t nrows, int64_t ncols, int64_t nn
   const size_t ne = (size_t)std::max<int64_t>(nnz, 1);
   auto& S = ctx->rect_side[P];
   auto& T = ctx->rect_side[1 - P];
-  HIPC(hipMalloc(&S.rowptr, (rows + 1) * sizeof(int64_t)));
-  HIPC(hipMalloc(&S.col, ne * sizeof(int32_t)));
-  HIPC(hipMalloc(&S.val, ne * sizeof(double)));
-  HIPC(hipMalloc(&T.rowptr, (ids + 1) * sizeof(int64_t)));
-  HIPC(hipMalloc(&T.col, ne * sizeof(int32_t)));
-  HIPC(hipMalloc(&T.val, ne * sizeof(double)));
+  HIPC(S.rowptr.alloc(rows + 1));
+  HIPC(S.col.alloc(ne));
+  HIPC(S.val.alloc(ne));
+  HIPC(T.rowptr.alloc(ids + 1));
+  HIPC(T.col.alloc(ne));
+  HIPC(T.val.alloc(ne));
   HIPC(hipMemcpy(S.rowptr, rp.data(), (rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   if (nnz) {
     HIPC(hipMemcpy(S.col, ci.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -3223,30 +3229,30 @@ static int rect_apply_host(rbl_ctx* ctx, int trans, int w, const double* X, doub
   shifted = shifted && ctx->rect_shift;
   const double* sa = !shifted ? nullptr : trans ? ctx->d_shift_v : ctx->d_shift_u;    // per output row
   const double* sin = !shifted ? nullptr : trans ? ctx->d_shift_u : ctx->d_shift_v;   // per input row
-  DevBuf x, xr, y, sc, sw, part;
+  DevBuf<double> x, xr, y, sc, sw, part;
   if (shifted) {
-    HIPC(hipMalloc(&sw.p, w * sizeof(double)));
-    HIPC(hipMalloc(&part.p, (size_t)rect_colsum_grid(rin, w) * w * sizeof(double)));
+    HIPC(sw.alloc(w));
+    HIPC(part.alloc((size_t)rect_colsum_grid(rin, w) * w));
   }
   const int64_t rmax = std::max(rin, rout);
-  HIPC(hipMalloc(&x.p, rmax * w * sizeof(double)));
-  HIPC(hipMalloc(&xr.p, rin * w * sizeof(double)));
-  HIPC(hipMalloc(&y.p, rout * w * sizeof(double)));
+  HIPC(x.alloc(rmax * w));
+  HIPC(xr.alloc(rin * w));
+  HIPC(y.alloc(rout * w));
   if (scale) {
-    HIPC(hipMalloc(&sc.p, w * sizeof(double)));
-    HIPC(hipMemcpyAsync(sc.p, scale, w * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPC(sc.alloc(w));
+    HIPC(hipMemcpyAsync(sc, scale, w * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   }
-  HIPC(hipMemcpyAsync(x.p, X, rin * w * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  colmajor_to_rowmajor(x.d(), rin, w, xr.d(), ctx->stream);
+  HIPC(hipMemcpyAsync(x, X, rin * w * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  colmajor_to_rowmajor(x, rin, w, xr, ctx->stream);
   {
     StageScope t(ctx, RBL_STAGE_AQ);
-    if (shifted) rect_colsum(rin, w, sin, xr.d(), part.d(), sw.d(), ctx->stream);
-    spmm_rect(rect_tier(ctx, trans), xr.d(), w, y.d(), nullptr, nullptr, sc.d(), ctx->stream, sa,
-              sw.d());
+    if (shifted) rect_colsum(rin, w, sin, xr, part, sw, ctx->stream);
+    spmm_rect(rect_tier(ctx, trans), xr, w, y, nullptr, nullptr, sc, ctx->stream, sa,
+              sw);
   }
   HIPC(hipGetLastError());
-  rowmajor_to_colmajor(y.d(), rout, w, x.d(), ctx->stream);
-  HIPC(hipMemcpyAsync(Y, x.p, rout * w * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  rowmajor_to_colmajor(y, rout, w, x, ctx->stream);
+  HIPC(hipMemcpyAsync(Y, x, rout * w * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   harvest_timers(ctx);
   return RBL_OK;
@@ -3288,8 +3294,8 @@ int rbl_set_rect_shift(rbl_ctx* ctx, const double* u, const double* v) {
   for (int64_t i = 0; i < n; ++i)
     if (!std::isfinite(v[i])) return fail(ctx, RBL_ERR_INVALID, "rbl_set_rect_shift: v has a non-finite entry");
   HIPC(hipStreamSynchronize(ctx->stream));  // steps in flight still read the old vectors
-  if (!ctx->d_shift_u) HIPC(hipMalloc(&ctx->d_shift_u, m * sizeof(double)));
-  if (!ctx->d_shift_v) HIPC(hipMalloc(&ctx->d_shift_v, n * sizeof(double)));
+  if (!ctx->d_shift_u) HIPC(ctx->d_shift_u.alloc(m));
+  if (!ctx->d_shift_v) HIPC(ctx->d_shift_v.alloc(n));
   HIPC(hipMemcpy(ctx->d_shift_u, u, m * sizeof(double), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(ctx->d_shift_v, v, n * sizeof(double), hipMemcpyHostToDevice));
   ctx->rect_shift = true;
@@ -3382,45 +3388,44 @@ int rbl_apply(rbl_ctx* ctx, int b, const double* X, double* Y) {
     return fail(ctx, RBL_ERR_STATE, "rbl_apply: b differs from the running Krylov block size");
   HIPC(hipSetDevice(ctx->device));
   const int64_t nl = std::max<int64_t>(ctx->nloc, 1);
-  DevBuf x, xr, y, ext;
-  HIPC(hipMalloc(&x.p, nl * b * sizeof(double)));
-  HIPC(hipMalloc(&xr.p, nl * b * sizeof(double)));
-  HIPC(hipMalloc(&y.p, (nl + kRowPad) * b * sizeof(double)));
-  HIPC(hipMemcpyAsync(x.p, X, ctx->nloc * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  colmajor_to_rowmajor(x.d(), ctx->nloc, b, xr.d(), ctx->stream);
-  const double* Qin = xr.d();
+  DevBuf<double> x, xr, y, ext;
+  HIPC(x.alloc(nl * b));
+  HIPC(xr.alloc(nl * b));
+  HIPC(y.alloc((nl + kRowPad) * b));
+  HIPC(hipMemcpyAsync(x, X, ctx->nloc * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  colmajor_to_rowmajor(x, ctx->nloc, b, xr, ctx->stream);
+  const double* Qin = xr;
   int64_t off = 0;
-  DevBuf sendbuf;
+  DevBuf<double> sendbuf;
   if (ctx->nranks > 1) {  // halo exchange through a private extended buffer
     const int64_t ext_rows = qext_rows(ctx, b);
-    HIPC(hipMalloc(&ext.p, ext_rows * b * sizeof(double)));
+    HIPC(ext.alloc(ext_rows * b));
     // rows between the received ranges stay finite (band-tile kernel multiplies them by 0)
-    HIPC(hipMemsetAsync(ext.p, 0, ext_rows * b * sizeof(double), ctx->stream));
+    HIPC(hipMemsetAsync(ext, 0, ext_rows * b * sizeof(double), ctx->stream));
     if (use_ghost(ctx, b))
-      HIPC(hipMalloc(&sendbuf.p, std::max<int64_t>(ctx->n_send, 1) * b * sizeof(double)));
-    double* keep_ext = ctx->d_qext;
-    const size_t keep_cap = ctx->qext_cap;
-    double* keep_send = ctx->d_sendbuf;
-    const int keep_b = ctx->b;
-    ctx->d_qext = ext.d();
-    ctx->qext_cap = (size_t)ext_rows * b;
-    ctx->d_sendbuf = sendbuf.d();
-    ctx->b = b;
-    const int st = halo_exchange(ctx, xr.d(), &Qin, &off);
-    ctx->d_qext = keep_ext;
-    ctx->qext_cap = keep_cap;
-    ctx->d_sendbuf = keep_send;
-    ctx->b = keep_b;
+      HIPC(sendbuf.alloc(std::max<int64_t>(ctx->n_send, 1) * b));
+    // the run's buffers and b step aside for the call's own, and come back whatever it returns
+    size_t cap = (size_t)ext_rows * b;
+    int bb = b;
+    auto trade = [&] {
+      std::swap(ctx->d_qext, ext);
+      std::swap(ctx->qext_cap, cap);
+      std::swap(ctx->d_sendbuf, sendbuf);
+      std::swap(ctx->b, bb);
+    };
+    trade();
+    const int st = halo_exchange(ctx, xr, &Qin, &off);
+    trade();
     if (st < 0) return st;
   }
   {
-    const int st = apply_A(ctx, Qin, off, b, y.d(), nullptr, nullptr, nullptr);
+    const int st = apply_A(ctx, Qin, off, b, y, nullptr, nullptr, nullptr);
     if (st < 0) return st;
   }
   HIPC(hipGetLastError());
-  CHK(push_halo(ctx, xr.d(), b, y.d()));
-  rowmajor_to_colmajor(y.d(), ctx->nloc, b, x.d(), ctx->stream);
-  HIPC(hipMemcpyAsync(Y, x.p, ctx->nloc * b * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  CHK(push_halo(ctx, xr, b, y));
+  rowmajor_to_colmajor(y, ctx->nloc, b, x, ctx->stream);
+  HIPC(hipMemcpyAsync(Y, x, ctx->nloc * b * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   return RBL_OK;
 }
@@ -3513,57 +3518,47 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   ctx->basis_bits = basis_bits;
   ctx->auto_planned = ctx->dev_blocks_opt < 0;
   if (basis_bits == 64) {
-    HIPC(hipMalloc(&ctx->d_basis, (size_t)dev_slots * nl * b * sizeof(double)));
+    HIPC(ctx->d_basis.alloc((size_t)dev_slots * nl * b));
     if (dev_slots < max_blocks + 1) {  // host spill: pinned slots for blocks resident..max_blocks
       ctx->resident = dev_slots - 2;
       // non-coherent pinned pages: the DMA engines stream them at PCIe rate both ways
-      ctx->h_spill.assign(max_blocks + 1 - ctx->resident, nullptr);
-      HIPC(hipMalloc(&ctx->d_stage, (size_t)nl * b * sizeof(double)));
-      if (!ctx->cstream) {
-        HIPC(hipStreamCreateWithFlags(&ctx->cstream, hipStreamNonBlocking));
-        HIPC(hipEventCreateWithFlags(&ctx->ev_fin, hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&ctx->ev_d2h[0], hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&ctx->ev_d2h[1], hipEventDisableTiming));
-      }
+      ctx->h_spill = std::vector<PinBuf<char>>(max_blocks + 1 - ctx->resident);
+      HIPC(ctx->d_stage.alloc((size_t)nl * b));
+      CHK(ensure_spill_stream(ctx));
     }
   } else {
     // + kRowPad32 zeroed pad rows, and every slot zeroed once: the fp32 Gram kernel's shifted
     // chunks may read rows past a tiny slice (reorth32.hip), which must be finite
-    const size_t bytes32 = ((size_t)dev_slots * nl + kRowPad32) * b * sizeof(float);
-    HIPC(hipMalloc(&ctx->d_basis32, bytes32));
-    HIPC(hipMemsetAsync(ctx->d_basis32, 0, bytes32, ctx->stream));
+    const size_t len32 = ((size_t)dev_slots * nl + kRowPad32) * b;
+    HIPC(ctx->d_basis32.alloc(len32));
+    HIPC(hipMemsetAsync(ctx->d_basis32, 0, len32 * sizeof(float), ctx->stream));
     if (dev_slots < max_blocks + 1) {  // host spill of the FLOAT basis (RBL_gpu.jl:59-81)
       ctx->resident = dev_slots - 2;
-      ctx->h_spill.assign(max_blocks + 1 - ctx->resident, nullptr);
+      ctx->h_spill = std::vector<PinBuf<char>>(max_blocks + 1 - ctx->resident);
       // + kRowPad32 zero rows like the slots (the Gram's shifted chunks)
-      HIPC(hipMalloc(&ctx->d_stage32, ((size_t)nl + kRowPad32) * b * sizeof(float)));
+      HIPC(ctx->d_stage32.alloc(((size_t)nl + kRowPad32) * b));
       HIPC(hipMemsetAsync(ctx->d_stage32, 0, ((size_t)nl + kRowPad32) * b * sizeof(float), ctx->stream));
-      if (!ctx->cstream) {
-        HIPC(hipStreamCreateWithFlags(&ctx->cstream, hipStreamNonBlocking));
-        HIPC(hipEventCreateWithFlags(&ctx->ev_fin, hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&ctx->ev_d2h[0], hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&ctx->ev_d2h[1], hipEventDisableTiming));
-      }
+      CHK(ensure_spill_stream(ctx));
     }
-    HIPC(hipMalloc(&ctx->d_Qi64, (nl + kRowPad) * b * sizeof(double)));
+    HIPC(ctx->d_Qi64.alloc((nl + kRowPad) * b));
     // the widened Q_{i-1}: only when the SpMM cannot read the fp32 blocks directly
-    if (!direct32_ok(ctx, b)) HIPC(hipMalloc(&ctx->d_Qm64, (nl + kRowPad) * b * sizeof(double)));
+    if (!direct32_ok(ctx, b)) HIPC(ctx->d_Qm64.alloc((nl + kRowPad) * b));
   }
-  HIPC(hipMalloc(&ctx->d_U, (nl + kRowPad) * b * sizeof(double)));
+  HIPC(ctx->d_U.alloc((nl + kRowPad) * b));
   ctx->T_cols = b;
-  HIPC(hipMalloc(&ctx->d_T, nl * b * sizeof(double)));
+  HIPC(ctx->d_T.alloc(nl * b));
   if (ctx->nranks > 1) {
     CHK(ensure_qext(ctx, b, ctx->stream));
     if (ctx->ghost)
-      HIPC(hipMalloc(&ctx->d_sendbuf, std::max<int64_t>(ctx->n_send, 1) * b * sizeof(double)));
+      HIPC(ctx->d_sendbuf.alloc(std::max<int64_t>(ctx->n_send, 1) * b));
   }
   const size_t slab = gram_slab_elems(ctx, b, max_blocks, basis_bits);
   ctx->slab_elems = slab;
-  HIPC(hipMalloc(&ctx->d_slab, slab * sizeof(double)));
+  HIPC(ctx->d_slab.alloc(slab));
   ctx->C_elems = (size_t)std::max(1, max_blocks) * b * 2 * b;
-  HIPC(hipMalloc(&ctx->d_C, ctx->C_elems * sizeof(double)));
-  HIPC(hipMalloc(&ctx->d_small, (size_t)S_NSMALL * b * b * sizeof(double)));
-  HIPC(hipMalloc(&ctx->d_flags, 4 * sizeof(int)));
+  HIPC(ctx->d_C.alloc(ctx->C_elems));
+  HIPC(ctx->d_small.alloc((size_t)S_NSMALL * b * b));
+  HIPC(ctx->d_flags.alloc(4));
   HIPC(hipMemset(ctx->d_flags, 0, 4 * sizeof(int)));
   {
 #ifdef RBL_VARIANTS
@@ -3573,8 +3568,8 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
     ctx->stash_direct = true;
 #endif
     const unsigned hf = ctx->stash_direct ? (hipHostMallocMapped | hipHostMallocCoherent) : hipHostMallocDefault;
-    HIPC(hipHostMalloc(&ctx->h_pin, stash_rec(b) * sizeof(double), hf));
-    HIPC(hipHostMalloc(&ctx->h_hist, (size_t)(max_blocks + 2) * stash_rec(b) * sizeof(double), hf));
+    HIPC(ctx->h_pin.alloc(stash_rec(b), hf));
+    HIPC(ctx->h_hist.alloc((size_t)(max_blocks + 2) * stash_rec(b), hf));
     if ((size_t)ctx->nloc * b * sizeof(double) >= 4 * kD2HPiece && !d2h_direct()) {
       CHK(ensure_d2h_slots(ctx));
       CHK(ensure_ritz_stream(ctx));
@@ -3583,7 +3578,7 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
       HIPC(hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->dv_pin), ctx->h_pin, 0));
       HIPC(hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->dv_hist), ctx->h_hist, 0));
     } else {
-      HIPC(hipMalloc(&ctx->d_stash, stash_rec(b) * sizeof(double)));
+      HIPC(ctx->d_stash.alloc(stash_rec(b)));
     }
   }
   }
@@ -4203,19 +4198,19 @@ int rbl_ritz(rbl_ctx* ctx, int nblocks, int k, const double* S, double* V_out) {
   // (n_local x b) takes V, T the column-major copy, the coefficient buffer (max_blocks b x 2b)
   // the S rows — no 2 x n_local x kcp allocation per call (at C4a 3.2 GB, whose hipMalloc +
   // first touch cost up to ~20 ms of a time-to-k)
-  DevBuf own_S, own_V, own_Vcm;
+  DevBuf<double> own_S, own_V, own_Vcm;
   double *pS = nullptr, *pV = nullptr, *pVcm = nullptr;
   if (kcp <= b && ctx->d_U && ctx->d_T && ctx->d_C && (size_t)rows * kcp <= ctx->C_elems) {
     pS = ctx->d_C;
     pV = ctx->d_U;
     pVcm = ctx->d_T;
   } else {
-    HIPC(hipMalloc(&own_S.p, rows * kcp * sizeof(double)));
-    HIPC(hipMalloc(&own_V.p, nl * kcp * sizeof(double)));
-    HIPC(hipMalloc(&own_Vcm.p, nl * kcp * sizeof(double)));
-    pS = own_S.d();
-    pV = own_V.d();
-    pVcm = own_Vcm.d();
+    HIPC(own_S.alloc(rows * kcp));
+    HIPC(own_V.alloc(nl * kcp));
+    HIPC(own_Vcm.alloc(nl * kcp));
+    pS = own_S;
+    pV = own_V;
+    pVcm = own_Vcm;
   }
   if (trace) t_alloc = tnow() - t0;
   const bool pipelined = V_out && ctx->nloc > 0 && kc >= k && pV == ctx->d_U &&
@@ -4335,25 +4330,24 @@ int rbl_apply_filter(rbl_ctx* ctx, int b, const double* X, double* Y) {
     return fail(ctx, RBL_ERR_INVALID, "rbl_apply_filter: one rank and a square A only");
   HIPC(hipSetDevice(ctx->device));
   const int64_t nl = std::max<int64_t>(ctx->nloc, 1);
-  const size_t padded = (size_t)(nl + kRowPad) * b * sizeof(double);
-  DevBuf x, xr, y, f0, f1, f2;
-  HIPC(hipMalloc(&x.p, nl * b * sizeof(double)));
-  HIPC(hipMalloc(&xr.p, nl * b * sizeof(double)));
-  for (DevBuf* p : {&y, &f0, &f1, &f2}) {
-    if (p == &f2 && !has_series(ctx)) continue;  // the series' third block
-    HIPC(hipMalloc(&p->p, padded));
-    HIPC(hipMemsetAsync(p->p, 0, padded, ctx->stream));
+  const size_t padded = (size_t)(nl + kRowPad) * b;
+  DevBuf<double> x, xr, y, F[3];
+  HIPC(x.alloc(nl * b));
+  HIPC(xr.alloc(nl * b));
+  for (DevBuf<double>* p : {&y, &F[0], &F[1], &F[2]}) {
+    if (p == &F[2] && !has_series(ctx)) continue;  // the series' third block
+    HIPC(p->alloc(padded));
+    HIPC(hipMemsetAsync(*p, 0, padded * sizeof(double), ctx->stream));
   }
-  double* const F[3] = {f0.d(), f1.d(), f2.d()};
-  HIPC(hipMemcpyAsync(x.p, X, ctx->nloc * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  colmajor_to_rowmajor(x.d(), ctx->nloc, b, xr.d(), ctx->stream);
+  HIPC(hipMemcpyAsync(x, X, ctx->nloc * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  colmajor_to_rowmajor(x, ctx->nloc, b, xr, ctx->stream);
   {
     StageScope t(ctx, RBL_STAGE_AQ);
-    CHK(filter_apply(ctx, xr.d(), b, y.d(), F));
+    CHK(filter_apply(ctx, xr, b, y, F));
   }
   HIPC(hipGetLastError());
-  rowmajor_to_colmajor(y.d(), ctx->nloc, b, x.d(), ctx->stream);
-  HIPC(hipMemcpyAsync(Y, x.p, ctx->nloc * b * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  rowmajor_to_colmajor(y, ctx->nloc, b, x, ctx->stream);
+  HIPC(hipMemcpyAsync(Y, x, ctx->nloc * b * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   harvest_timers(ctx);
   return RBL_OK;
@@ -4367,22 +4361,22 @@ int rbl_bench_series_pass(rbl_ctx* ctx, int64_t len, int reps, double* fused_ms,
   if (!ctx || len < 1 || reps < 1 || !fused_ms || !pair_ms)
     return fail(ctx, RBL_ERR_INVALID, "rbl_bench_series_pass: bad arguments");
   HIPC(hipSetDevice(ctx->device));
-  DevBuf w, t1, t2, acc;
+  DevBuf<double> w, t1, t2, acc;
   const size_t bytes = (size_t)len * sizeof(double);
-  for (DevBuf* p : {&w, &t1, &t2, &acc}) {
-    HIPC(hipMalloc(&p->p, bytes));
-    HIPC(hipMemsetAsync(p->p, 0, bytes, ctx->stream));
+  for (DevBuf<double>* p : {&w, &t1, &t2, &acc}) {
+    HIPC(p->alloc((size_t)len));
+    HIPC(hipMemsetAsync(*p, 0, bytes, ctx->stream));
   }
   const double al = 0.5, be = 0.25, mu = 1e-3;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIPC(hipEventCreate(&e0));
   HIPC(hipEventCreate(&e1));
   auto fused = [&] {
-    cheb_series_term(len, w.d(), t1.d(), t2.d(), al, be, mu, 0.0, w.d(), acc.d(), false, false, ctx->stream);
+    cheb_series_term(len, w, t1, t2, al, be, mu, 0.0, w, acc, false, false, ctx->stream);
   };
   auto pair = [&] {
-    cheb_axpby(len, w.d(), t1.d(), t2.d(), al, be, -1.0, w.d(), ctx->stream);
-    cheb_axpby(len, acc.d(), w.d(), nullptr, 1.0, mu, 0.0, acc.d(), ctx->stream);  // out may be W
+    cheb_axpby(len, w, t1, t2, al, be, -1.0, w, ctx->stream);
+    cheb_axpby(len, acc, w, nullptr, 1.0, mu, 0.0, acc, ctx->stream);  // out may be W
   };
   int st = RBL_OK;
   auto timed = [&](auto&& fn, double* out) {
@@ -4440,8 +4434,8 @@ int rbl_set_lowrank(rbl_ctx* ctx, int r, const double* P, const double* S) {
     for (int64_t i = 0; i < n; ++i) Pr[(size_t)i * rp + j] = P[i + (size_t)j * n];
   HIPC(hipStreamSynchronize(ctx->stream));  // steps in flight still read the old update
   free_lowrank(ctx);
-  HIPC(hipMalloc(&ctx->d_lr_P, Pr.size() * sizeof(double)));
-  HIPC(hipMalloc(&ctx->d_lr_S, (size_t)r * r * sizeof(double)));
+  HIPC(ctx->d_lr_P.alloc(Pr.size()));
+  HIPC(ctx->d_lr_S.alloc((size_t)r * r));
   HIPC(hipMemcpy(ctx->d_lr_P, Pr.data(), Pr.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(ctx->d_lr_S, S, (size_t)r * r * sizeof(double), hipMemcpyHostToDevice));  // S = S^T
   ctx->lr_r = r;
@@ -4478,22 +4472,22 @@ int rbl_bench_lowrank_pass(rbl_ctx* ctx, int64_t rows, int b, int r, int reps, d
   HIPC(hipSetDevice(ctx->device));
   const int rp = lr_padded_width(r);
   const size_t grid = (size_t)lr_project_grid(rows, b, rp);
-  DevBuf x, u, p, wc, part;
-  const std::pair<DevBuf*, size_t> bufs[] = {{&x, (size_t)rows * b},
+  DevBuf<double> x, u, p, wc, part;
+  const std::pair<DevBuf<double>*, size_t> bufs[] = {{&x, (size_t)rows * b},
                                              {&u, (size_t)rows * b},
                                              {&p, (size_t)rows * rp},
                                              {&wc, (size_t)2 * rp * b},
                                              {&part, grid * rp * b}};
   for (const auto& q : bufs) {
-    HIPC(hipMalloc(&q.first->p, q.second * sizeof(double)));
-    HIPC(hipMemsetAsync(q.first->p, 0, q.second * sizeof(double), ctx->stream));
+    HIPC(q.first->alloc(q.second));
+    HIPC(hipMemsetAsync(*q.first, 0, q.second * sizeof(double), ctx->stream));
   }
-  double *w = wc.d(), *c = wc.d() + (size_t)rp * b;
+  double *w = wc, *c = wc + (size_t)rp * b;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIPC(hipEventCreate(&e0));
   HIPC(hipEventCreate(&e1));
-  auto project = [&] { lr_project(rows, b, rp, p.d(), x.d(), part.d(), w, ctx->stream); };
-  auto update = [&] { lr_update(rows, b, rp, p.d(), c, u.d(), ctx->stream); };
+  auto project = [&] { lr_project(rows, b, rp, p, x, part, w, ctx->stream); };
+  auto update = [&] { lr_update(rows, b, rp, p, c, u, ctx->stream); };
   int st = RBL_OK;
   auto timed = [&](auto&& fn, double* out) {
     fn();  // warm-up
@@ -4539,37 +4533,37 @@ int rbl_cheb_moments(rbl_ctx* ctx, int b, int degree, double lo, double hi, cons
     return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_moments: not with a rectangular B (rbl_set_matrix_normal)");
   HIPC(hipSetDevice(ctx->device));
   const int64_t n = ctx->nloc, nl = std::max<int64_t>(n, 1);
-  const size_t padded = (size_t)(nl + kRowPad) * b * sizeof(double);
+  const size_t padded = (size_t)(nl + kRowPad) * b;
   const size_t nmom = (size_t)(2 * degree + 1) * b;
   const int grid = moment_grid(n, b);
-  DevBuf f[3], slab, dots;
-  for (DevBuf& p : f) {
-    HIPC(hipMalloc(&p.p, padded));
-    HIPC(hipMemsetAsync(p.p, 0, padded, ctx->stream));
+  DevBuf<double> f[3], slab, dots;
+  for (DevBuf<double>& p : f) {
+    HIPC(p.alloc(padded));
+    HIPC(hipMemsetAsync(p, 0, padded * sizeof(double), ctx->stream));
   }
-  HIPC(hipMalloc(&slab.p, (size_t)grid * 3 * b * sizeof(double)));
-  HIPC(hipMalloc(&dots.p, nmom * sizeof(double)));
+  HIPC(slab.alloc((size_t)grid * 3 * b));
+  HIPC(dots.alloc(nmom));
   if (X) {  // column-major through f[1], which the first SpMM overwrites
-    HIPC(hipMemcpyAsync(f[1].p, X, n * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    colmajor_to_rowmajor(f[1].d(), n, b, f[0].d(), ctx->stream);
+    HIPC(hipMemcpyAsync(f[1], X, n * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    colmajor_to_rowmajor(f[1], n, b, f[0], ctx->stream);
   } else {
-    randn_block(f[0].d(), n, b, ctx->r0, seed, ctx->stream, ctx->relabeled ? &ctx->relabel_perm : nullptr);
+    randn_block(f[0], n, b, ctx->r0, seed, ctx->stream, ctx->relabeled ? &ctx->relabel_perm : nullptr);
   }
   HIPC(hipGetLastError());
   const double c = 0.5 * (lo + hi), e = 0.5 * (hi - lo);
   {
     StageScope t(ctx, RBL_STAGE_AQ);
-    const double* t1 = f[0].d();  // t_{j-1}
+    const double* t1 = f[0];  // t_{j-1}
     const double* t2 = nullptr;   // t_{j-2}
-    double* dj = dots.d();
+    double* dj = dots;
     for (int j = 1; j <= degree; ++j) {
-      double* tj = f[j % 3].d();
+      double* tj = f[j % 3];
       const int st = apply_A(ctx, t1, 0, b, tj, nullptr, nullptr, nullptr);
       if (st < 0) return st;
       const double al = (j == 1 ? 1.0 : 2.0) / e;
       const int nq = j == 1 ? 3 : 2;
-      cheb_moment_term(n, b, tj, t1, t2, al, -al * c, tj, slab.d(), grid, j == 1, j == degree, ctx->stream);
-      reduce_slab(slab.d(), grid, (int64_t)nq * b, dj, nullptr, ctx->stream);
+      cheb_moment_term(n, b, tj, t1, t2, al, -al * c, tj, slab, grid, j == 1, j == degree, ctx->stream);
+      reduce_slab(slab, grid, (int64_t)nq * b, dj, nullptr, ctx->stream);
       HIPC(hipGetLastError());
       dj += (size_t)nq * b;
       t2 = t1;
@@ -4577,7 +4571,7 @@ int rbl_cheb_moments(rbl_ctx* ctx, int b, int degree, double lo, double hi, cons
     }
   }
   std::vector<double> d(nmom);
-  HIPC(hipMemcpyAsync(d.data(), dots.p, nmom * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(d.data(), dots, nmom * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   harvest_timers(ctx);
   const size_t ld = (size_t)2 * degree + 1;
@@ -4605,21 +4599,21 @@ int rbl_bench_moment_pass(rbl_ctx* ctx, int64_t len_rows, int b, int reps, doubl
     return fail(ctx, RBL_ERR_INVALID, "rbl_bench_moment_pass: bad arguments");
   HIPC(hipSetDevice(ctx->device));
   const int grid = moment_grid(len_rows, b);
-  DevBuf w, t1, t2, slab, dots;
+  DevBuf<double> w, t1, t2, slab, dots;
   const size_t bytes = (size_t)len_rows * b * sizeof(double);
-  for (DevBuf* p : {&w, &t1, &t2}) {
-    HIPC(hipMalloc(&p->p, bytes));
-    HIPC(hipMemsetAsync(p->p, 0, bytes, ctx->stream));
+  for (DevBuf<double>* p : {&w, &t1, &t2}) {
+    HIPC(p->alloc((size_t)len_rows * b));
+    HIPC(hipMemsetAsync(*p, 0, bytes, ctx->stream));
   }
-  HIPC(hipMalloc(&slab.p, (size_t)grid * 2 * b * sizeof(double)));
-  HIPC(hipMalloc(&dots.p, (size_t)2 * b * sizeof(double)));
+  HIPC(slab.alloc((size_t)grid * 2 * b));
+  HIPC(dots.alloc((size_t)2 * b));
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIPC(hipEventCreate(&e0));
   HIPC(hipEventCreate(&e1));
   auto pass = [&] {
-    cheb_moment_term(len_rows, b, w.d(), t1.d(), t2.d(), 0.5, 0.25, w.d(), slab.d(), grid, false, false,
+    cheb_moment_term(len_rows, b, w, t1, t2, 0.5, 0.25, w, slab, grid, false, false,
                      ctx->stream);
-    reduce_slab(slab.d(), grid, (int64_t)2 * b, dots.d(), nullptr, ctx->stream);
+    reduce_slab(slab, grid, (int64_t)2 * b, dots, nullptr, ctx->stream);
   };
   int st = RBL_OK;
   pass();  // warm-up
@@ -4665,51 +4659,51 @@ int rbl_cheb_diag(rbl_ctx* ctx, int b, int degree, double lo, double hi, int nf,
     return fail(ctx, RBL_ERR_INVALID, "rbl_cheb_diag: not with a rectangular B (rbl_set_matrix_normal)");
   HIPC(hipSetDevice(ctx->device));
   const int64_t n = ctx->nloc, nl = std::max<int64_t>(n, 1);
-  const size_t padded = (size_t)(nl + kRowPad) * b * sizeof(double);
+  const size_t padded = (size_t)(nl + kRowPad) * b;
   // term-major on the device: term j's nf coefficients contiguous
   std::vector<double> cj(ncoef);
   for (int e = 0; e < nf; ++e)
     for (int j = 0; j <= degree; ++j) cj[(size_t)j * nf + e] = coef[(size_t)e * (degree + 1) + j];
-  DevBuf f[3], xb, dd, dcm, dq, dcoef;
-  for (DevBuf* p : {&f[0], &f[1], &f[2], &xb}) {
-    HIPC(hipMalloc(&p->p, padded));
-    HIPC(hipMemsetAsync(p->p, 0, padded, ctx->stream));
+  DevBuf<double> f[3], xb, dd, dcm, dq, dcoef;
+  for (DevBuf<double>* p : {&f[0], &f[1], &f[2], &xb}) {
+    HIPC(p->alloc(padded));
+    HIPC(hipMemsetAsync(*p, 0, padded * sizeof(double), ctx->stream));
   }
-  HIPC(hipMalloc(&dd.p, (size_t)nl * nf * sizeof(double)));
-  HIPC(hipMalloc(&dcm.p, (size_t)nl * nf * sizeof(double)));
-  HIPC(hipMalloc(&dq.p, (size_t)nl * sizeof(double)));
-  HIPC(hipMalloc(&dcoef.p, ncoef * sizeof(double)));
-  HIPC(hipMemcpyAsync(dcoef.p, cj.data(), ncoef * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(dd.alloc((size_t)nl * nf));
+  HIPC(dcm.alloc((size_t)nl * nf));
+  HIPC(dq.alloc((size_t)nl));
+  HIPC(dcoef.alloc(ncoef));
+  HIPC(hipMemcpyAsync(dcoef, cj.data(), ncoef * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if (X) {  // column-major through f[1], which the first SpMM overwrites
-    HIPC(hipMemcpyAsync(f[1].p, X, n * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    colmajor_to_rowmajor(f[1].d(), n, b, xb.d(), ctx->stream);
+    HIPC(hipMemcpyAsync(f[1], X, n * b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    colmajor_to_rowmajor(f[1], n, b, xb, ctx->stream);
   } else {
-    randn_block(xb.d(), n, b, ctx->r0, seed, ctx->stream, ctx->relabeled ? &ctx->relabel_perm : nullptr);
-    if (probe == RBL_PROBE_SIGN) sign_block(n * b, xb.d(), ctx->stream);
+    randn_block(xb, n, b, ctx->r0, seed, ctx->stream, ctx->relabeled ? &ctx->relabel_perm : nullptr);
+    if (probe == RBL_PROBE_SIGN) sign_block(n * b, xb, ctx->stream);
   }
   HIPC(hipGetLastError());
   const double c = 0.5 * (lo + hi), e = 0.5 * (hi - lo);
   {
     StageScope t(ctx, RBL_STAGE_AQ);
-    const double* t1 = xb.d();   // t_{j-1}
+    const double* t1 = xb;   // t_{j-1}
     const double* t2 = nullptr;  // t_{j-2}
     for (int j = 1; j <= degree; ++j) {
-      double* tj = f[j % 3].d();
+      double* tj = f[j % 3];
       const int st = apply_A(ctx, t1, 0, b, tj, nullptr, nullptr, nullptr);
       if (st < 0) return st;
       const double al = (j == 1 ? 1.0 : 2.0) / e;
-      const double* cf = dcoef.d() + (j == 1 ? 0 : (size_t)j * nf);
-      cheb_diag_term(n, b, nf, tj, t1, t2, xb.d(), al, -al * c, tj, cf, dd.d(), dq.d(), j == 1, j == degree,
+      const double* cf = dcoef + (j == 1 ? 0 : (size_t)j * nf);
+      cheb_diag_term(n, b, nf, tj, t1, t2, xb, al, -al * c, tj, cf, dd, dq, j == 1, j == degree,
                      ctx->stream);
       HIPC(hipGetLastError());
       t2 = t1;
       t1 = tj;
     }
   }
-  rowmajor_to_colmajor(dd.d(), n, nf, dcm.d(), ctx->stream);
+  rowmajor_to_colmajor(dd, n, nf, dcm, ctx->stream);
   HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(num_out, dcm.p, n * nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPC(hipMemcpyAsync(den_out, dq.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(num_out, dcm, n * nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(den_out, dq, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   harvest_timers(ctx);
   return RBL_OK;
@@ -4723,23 +4717,23 @@ int rbl_bench_diag_pass(rbl_ctx* ctx, int64_t len_rows, int b, int nf, int reps,
   if (!ctx || len_rows < 1 || b < 1 || b > 256 || nf < 1 || nf > 32 || reps < 1 || !ms)
     return fail(ctx, RBL_ERR_INVALID, "rbl_bench_diag_pass: bad arguments");
   HIPC(hipSetDevice(ctx->device));
-  DevBuf w, t1, t2, x, dd, dq, dcoef;
+  DevBuf<double> w, t1, t2, x, dd, dq, dcoef;
   const size_t bytes = (size_t)len_rows * b * sizeof(double);
-  for (DevBuf* p : {&w, &t1, &t2, &x}) {
-    HIPC(hipMalloc(&p->p, bytes));
-    HIPC(hipMemsetAsync(p->p, 0, bytes, ctx->stream));
+  for (DevBuf<double>* p : {&w, &t1, &t2, &x}) {
+    HIPC(p->alloc((size_t)len_rows * b));
+    HIPC(hipMemsetAsync(*p, 0, bytes, ctx->stream));
   }
-  HIPC(hipMalloc(&dd.p, (size_t)len_rows * nf * sizeof(double)));
-  HIPC(hipMemsetAsync(dd.p, 0, (size_t)len_rows * nf * sizeof(double), ctx->stream));
-  HIPC(hipMalloc(&dq.p, (size_t)len_rows * sizeof(double)));
-  HIPC(hipMalloc(&dcoef.p, (size_t)nf * sizeof(double)));
+  HIPC(dd.alloc((size_t)len_rows * nf));
+  HIPC(hipMemsetAsync(dd, 0, (size_t)len_rows * nf * sizeof(double), ctx->stream));
+  HIPC(dq.alloc((size_t)len_rows));
+  HIPC(dcoef.alloc((size_t)nf));
   const std::vector<double> cf((size_t)nf, 1e-3);
-  HIPC(hipMemcpyAsync(dcoef.p, cf.data(), (size_t)nf * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dcoef, cf.data(), (size_t)nf * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIPC(hipEventCreate(&e0));
   HIPC(hipEventCreate(&e1));
   auto pass = [&] {
-    cheb_diag_term(len_rows, b, nf, w.d(), t1.d(), t2.d(), x.d(), 0.5, 0.25, w.d(), dcoef.d(), dd.d(), dq.d(),
+    cheb_diag_term(len_rows, b, nf, w, t1, t2, x, 0.5, 0.25, w, dcoef, dd, dq,
                    false, false, ctx->stream);
   };
   int st = RBL_OK;
@@ -4768,30 +4762,29 @@ int rbl_ritz_project(rbl_ctx* ctx, int nblocks, int k, const double* S, double* 
   if (k > nblocks * ctx->b) return fail(ctx, RBL_ERR_INVALID, "rbl_ritz_project: k > nblocks*b");
   HIPC(hipSetDevice(ctx->device));
   HIPC(hipStreamSynchronize(ctx->stream));
-  hipFree(ctx->d_rv);
-  hipFree(ctx->d_rw);
-  ctx->d_rv = ctx->d_rw = nullptr;
+  ctx->d_rv.reset();
+  ctx->d_rw.reset();
   ctx->ritz_k = 0;
   const int b = ctx->b;
   const int kp = (k + 1) & ~1;  // even width (16-B row stores), the pad column zero
   const int64_t rows = (int64_t)nblocks * b;
   const int64_t nl = std::max<int64_t>(ctx->nloc, 1);
   const size_t vbytes = (size_t)(nl + kRowPad) * kp * sizeof(double);
-  HIPC(hipMalloc(&ctx->d_rv, vbytes));
-  HIPC(hipMalloc(&ctx->d_rw, vbytes));
+  HIPC(ctx->d_rv.alloc((size_t)(nl + kRowPad) * kp));
+  HIPC(ctx->d_rw.alloc((size_t)(nl + kRowPad) * kp));
   HIPC(hipMemsetAsync(ctx->d_rv, 0, vbytes, ctx->stream));
   HIPC(hipMemsetAsync(ctx->d_rw, 0, vbytes, ctx->stream));
   // V = [Q_1..Q_nblocks] S, kept on the device
   std::vector<double> srm((size_t)rows * kp);
   for (int64_t r = 0; r < rows; ++r)
     for (int c = 0; c < kp; ++c) srm[(size_t)r * kp + c] = c < k ? S[(size_t)c * rows + r] : 0.0;
-  DevBuf dS;
-  HIPC(hipMalloc(&dS.p, rows * kp * sizeof(double)));
-  HIPC(hipMemcpyAsync(dS.p, srm.data(), rows * kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  DevBuf<double> dS;
+  HIPC(dS.alloc(rows * kp));
+  HIPC(hipMemcpyAsync(dS, srm.data(), rows * kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   {
     StageScope t(ctx, RBL_STAGE_RITZ);
-    if (ctx->basis_bits == 64) CHK(combine_blocks(ctx, nblocks, kp, dS.d(), ctx->d_rv));
-    else CHK(combine_blocks32(ctx, nblocks, kp, dS.d(), ctx->d_rv));
+    if (ctx->basis_bits == 64) CHK(combine_blocks(ctx, nblocks, kp, dS, ctx->d_rv));
+    else CHK(combine_blocks32(ctx, nblocks, kp, dS, ctx->d_rv));
   }
   // W = A V with the plain operator, in column chunks of the run's block size where that is
   // one the MFMA SpMM kernels take (b in {16, 32}; the only widths left once the CSR is
@@ -4804,18 +4797,18 @@ int rbl_ritz_project(rbl_ctx* ctx, int nblocks, int k, const double* S, double* 
       if (st < 0) return st;
     } else {
       const size_t cbytes = (size_t)(nl + kRowPad) * cw * sizeof(double);
-      DevBuf xc, yc;
-      HIPC(hipMalloc(&xc.p, cbytes));
-      HIPC(hipMalloc(&yc.p, cbytes));
-      HIPC(hipMemsetAsync(xc.p, 0, cbytes, ctx->stream));
-      HIPC(hipMemsetAsync(yc.p, 0, cbytes, ctx->stream));
+      DevBuf<double> xc, yc;
+      HIPC(xc.alloc((size_t)(nl + kRowPad) * cw));
+      HIPC(yc.alloc((size_t)(nl + kRowPad) * cw));
+      HIPC(hipMemsetAsync(xc, 0, cbytes, ctx->stream));
+      HIPC(hipMemsetAsync(yc, 0, cbytes, ctx->stream));
       for (int c0 = 0; c0 < kp; c0 += cw) {
         const int w = std::min(cw, kp - c0);
-        if (w < cw && c0 > 0) HIPC(hipMemsetAsync(xc.p, 0, cbytes, ctx->stream));
-        copy_cols(ctx->nloc, w, ctx->d_rv, kp, c0, xc.d(), cw, 0, ctx->stream);
-        const int st = apply_A(ctx, xc.d(), 0, cw, yc.d(), nullptr, nullptr, nullptr);
+        if (w < cw && c0 > 0) HIPC(hipMemsetAsync(xc, 0, cbytes, ctx->stream));
+        copy_cols(ctx->nloc, w, ctx->d_rv, kp, c0, xc, cw, 0, ctx->stream);
+        const int st = apply_A(ctx, xc, 0, cw, yc, nullptr, nullptr, nullptr);
         if (st < 0) return st;
-        copy_cols(ctx->nloc, w, yc.d(), cw, 0, ctx->d_rw, kp, c0, ctx->stream);
+        copy_cols(ctx->nloc, w, yc, cw, 0, ctx->d_rw, kp, c0, ctx->stream);
       }
       HIPC(hipGetLastError());
       HIPC(hipStreamSynchronize(ctx->stream));  // the chunk blocks leave scope
@@ -4827,13 +4820,13 @@ int rbl_ritz_project(rbl_ctx* ctx, int nblocks, int k, const double* S, double* 
   if (ctx->nloc > 0) {
     StageScope t(ctx, RBL_STAGE_RITZ);
     const int splits = gram_splits(ctx->nloc, 1, kp, kp);
-    DevBuf slab, dH;
-    HIPC(hipMalloc(&slab.p, (size_t)splits * kp * kp * sizeof(double)));
-    HIPC(hipMalloc(&dH.p, (size_t)kp * kp * sizeof(double)));
-    gram_partial(ctx->nloc, run1(ctx->d_rv, kp), pan1(ctx->d_rw, kp), slab.d(), splits, nullptr, ctx->stream);
-    reduce_slab(slab.d(), splits, (int64_t)kp * kp, dH.d(), nullptr, ctx->stream);
+    DevBuf<double> slab, dH;
+    HIPC(slab.alloc((size_t)splits * kp * kp));
+    HIPC(dH.alloc((size_t)kp * kp));
+    gram_partial(ctx->nloc, run1(ctx->d_rv, kp), pan1(ctx->d_rw, kp), slab, splits, nullptr, ctx->stream);
+    reduce_slab(slab, splits, (int64_t)kp * kp, dH, nullptr, ctx->stream);
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(h.data(), dH.p, (size_t)kp * kp * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipMemcpyAsync(h.data(), dH, (size_t)kp * kp * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
   }
   HIPC(hipStreamSynchronize(ctx->stream));
@@ -4869,26 +4862,26 @@ int rbl_ritz_finish_cols(rbl_ctx* ctx, int kproj, int k, const double* Y, const 
     for (int c = 0; c < k; ++c) yrm[(size_t)r * kp + c] = Y[(size_t)c * kproj + r];
   for (int c = 0; c < k; ++c) th[c] = theta[c];
   const int grid = resid_grid(ctx->nloc);
-  DevBuf dY, dTh, X, Z, part, dres;
-  HIPC(hipMalloc(&dY.p, (size_t)kpr * kp * sizeof(double)));
-  HIPC(hipMalloc(&dTh.p, kp * sizeof(double)));
-  HIPC(hipMalloc(&X.p, (size_t)nl * kp * sizeof(double)));
-  HIPC(hipMalloc(&Z.p, (size_t)nl * kp * sizeof(double)));
-  HIPC(hipMalloc(&part.p, (size_t)grid * kp * sizeof(double)));
-  HIPC(hipMalloc(&dres.p, kp * sizeof(double)));
-  HIPC(hipMemcpyAsync(dY.p, yrm.data(), (size_t)kpr * kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(dTh.p, th.data(), kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  DevBuf<double> dY, dTh, X, Z, part, dres;
+  HIPC(dY.alloc((size_t)kpr * kp));
+  HIPC(dTh.alloc(kp));
+  HIPC(X.alloc((size_t)nl * kp));
+  HIPC(Z.alloc((size_t)nl * kp));
+  HIPC(part.alloc((size_t)grid * kp));
+  HIPC(dres.alloc(kp));
+  HIPC(hipMemcpyAsync(dY, yrm.data(), (size_t)kpr * kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dTh, th.data(), kp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if (ctx->nloc > 0) {
     StageScope t(ctx, RBL_STAGE_RITZ);
     // X = V Y, Z = W Y; resid_j^2 = sum_r (Z - X diag(theta))^2[r, j]
-    CHK(tsmm_checked(ctx, run1(ctx->d_rv, kpr), dY.d(), kp, pan1(X.d(), kp), 1.0, 0.0, nullptr));
-    CHK(tsmm_checked(ctx, run1(ctx->d_rw, kpr), dY.d(), kp, pan1(Z.d(), kp), 1.0, 0.0, nullptr));
-    resid_partial(ctx->nloc, kp, Z.d(), X.d(), dTh.d(), part.d(), grid, ctx->stream);
-    reduce_slab(part.d(), grid, kp, dres.d(), nullptr, ctx->stream);
+    CHK(tsmm_checked(ctx, run1(ctx->d_rv, kpr), dY, kp, pan1(X, kp), 1.0, 0.0, nullptr));
+    CHK(tsmm_checked(ctx, run1(ctx->d_rw, kpr), dY, kp, pan1(Z, kp), 1.0, 0.0, nullptr));
+    resid_partial(ctx->nloc, kp, Z, X, dTh, part, grid, ctx->stream);
+    reduce_slab(part, grid, kp, dres, nullptr, ctx->stream);
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(res.data(), dres.p, kp * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipMemcpyAsync(res.data(), dres, kp * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (V_out) {  // W is spent: its block takes the column-major copy of X
-      rowmajor_to_colmajor(X.d(), ctx->nloc, kp, ctx->d_rw, ctx->stream);
+      rowmajor_to_colmajor(X, ctx->nloc, kp, ctx->d_rw, ctx->stream);
       HIPC(hipGetLastError());
       CHK(d2h_staged(ctx, V_out, ctx->d_rw, (size_t)ctx->nloc * k * sizeof(double)));
     }
@@ -4897,9 +4890,8 @@ int rbl_ritz_finish_cols(rbl_ctx* ctx, int kproj, int k, const double* Y, const 
   harvest_timers(ctx);
   if (resid_out)
     for (int c = 0; c < k; ++c) resid_out[c] = std::sqrt(res[c]);
-  hipFree(ctx->d_rv);
-  hipFree(ctx->d_rw);
-  ctx->d_rv = ctx->d_rw = nullptr;
+  ctx->d_rv.reset();
+  ctx->d_rw.reset();
   ctx->ritz_k = 0;
   return RBL_OK;
 }
@@ -4985,17 +4977,15 @@ int rbl_thick_restart(rbl_ctx* ctx, int nblocks, int keep_blocks, const double* 
   for (int64_t c = 0; c < p; ++c)
     for (int64_t r = 0; r < mb; ++r) Sr[(size_t)(r * p + c)] = S[r + c * mb];
   if (ctx->tr_S_cap < Sr.size()) {
-    hipFree(ctx->d_tr_S);
-    ctx->d_tr_S = nullptr;
+    ctx->d_tr_S.reset();
     ctx->tr_S_cap = 0;
-    HIPC(hipMalloc(&ctx->d_tr_S, Sr.size() * sizeof(double)));
+    HIPC(ctx->d_tr_S.alloc(Sr.size()));
     ctx->tr_S_cap = Sr.size();
   }
   if (ctx->arrow_W_cap < (size_t)(p * b)) {
-    hipFree(ctx->d_arrow_W);
-    ctx->d_arrow_W = nullptr;
+    ctx->d_arrow_W.reset();
     ctx->arrow_W_cap = 0;
-    HIPC(hipMalloc(&ctx->d_arrow_W, (size_t)(p * b) * sizeof(double)));
+    HIPC(ctx->d_arrow_W.alloc((size_t)(p * b)));
     ctx->arrow_W_cap = (size_t)(p * b);
   }
   HIPC(hipMemcpy(ctx->d_tr_S, Sr.data(), Sr.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -5037,16 +5027,16 @@ int rbl_bench_compress_pass(rbl_ctx* ctx, int64_t rows, int b, int m, int keep_b
   HIPC(hipSetDevice(ctx->device));
   const int p = keep_blocks * b;
   const int64_t slot = rows * b;
-  DevBuf x, s, y;
-  const std::pair<DevBuf*, size_t> bufs[] = {{&x, (size_t)slot * m},
+  DevBuf<double> x, s, y;
+  const std::pair<DevBuf<double>*, size_t> bufs[] = {{&x, (size_t)slot * m},
                                              {&s, (size_t)m * b * p},
                                              {&y, (size_t)rows * 64}};
   for (const auto& q : bufs) {
-    HIPC(hipMalloc(&q.first->p, q.second * sizeof(double)));
-    HIPC(hipMemsetAsync(q.first->p, 0, q.second * sizeof(double), ctx->stream));
+    HIPC(q.first->alloc(q.second));
+    HIPC(hipMemsetAsync(*q.first, 0, q.second * sizeof(double), ctx->stream));
   }
   PanelRun X;
-  X.base = x.d();
+  X.base = x;
   X.stride = slot;
   X.count = m;
   X.w = b;
@@ -5055,11 +5045,11 @@ int rbl_bench_compress_pass(rbl_ctx* ctx, int64_t rows, int b, int m, int keep_b
   HIPC(hipEventCreate(&e1));
   int st = RBL_OK;
   auto inplace = [&] {
-    if (!basis_compress(rows, X, s.d(), p, ctx->stream)) st = RBL_ERR_INVALID;
+    if (!basis_compress(rows, X, s, p, ctx->stream)) st = RBL_ERR_INVALID;
   };
   auto sliced = [&] {
     for (int c0 = 0; c0 < p; c0 += 64)
-      tsmm(rows, X, s.d() + c0, p, pan1(y.d(), std::min(64, p - c0)), 1.0, 0.0, nullptr, ctx->stream);
+      tsmm(rows, X, s + c0, p, pan1(y, std::min(64, p - c0)), 1.0, 0.0, nullptr, ctx->stream);
   };
   auto timed = [&](auto&& fn, double* out) {
     fn();  // warm-up
@@ -5089,14 +5079,13 @@ int rbl_lock(rbl_ctx* ctx, int nblocks, int nvec, const double* S) {
   const int64_t nl = std::max<int64_t>(ctx->nloc, 1);
   if (ctx->nlock + nvec > ctx->lock_cap) {
     const int cap = std::max(2 * ctx->lock_cap, ctx->nlock + nvec);
-    double* d = nullptr;
-    HIPC(hipMalloc(&d, (size_t)cap * nl * sizeof(double)));
+    DevBuf<double> d;
+    HIPC(d.alloc((size_t)cap * nl));
     if (ctx->nlock)
       HIPC(hipMemcpyAsync(d, ctx->d_lock, (size_t)ctx->nlock * nl * sizeof(double),
                           hipMemcpyDeviceToDevice, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->d_lock);
-    ctx->d_lock = d;
+    ctx->d_lock = std::move(d);
     ctx->lock_cap = cap;
   }
   const int64_t rows = (int64_t)nblocks * ctx->b;
