@@ -372,6 +372,29 @@ void lr_small(int r, int rp, int b, const double* S, const double* w, double* c,
 void lr_update(int64_t rows, int b, int rp, const double* P, const double* c, double* U,
                hipStream_t s);
 
+// --- kernelop.hip: the implicit kernel matrix (rbl_set_matrix_kernel) ---------------------------
+// Op = diag(scale) K diag(scale) + nugget I, K_ij = kappa(x_i, x_j) over the n points X (device,
+// row-major n x d4, d4 = 4 ceil(d / 4) <= kKernMaxDim, the columns past d zero; nrm[i] = |x_i|^2
+// from kernop_norms).  scale null: all ones.  kind: kKernRbf exp(-gamma |x-y|^2), kKernLaplace
+// exp(-gamma |x-y|), kKernPoly (gamma x.y + coef0)^degree (the values of RBL_KERNEL_*).
+constexpr int kKernRbf = 0, kKernLaplace = 1, kKernPoly = 2;
+constexpr int kKernMaxDim = 256;
+struct KernOp {
+  int64_t n = 0;
+  int d4 = 0;
+  int kind = kKernRbf;
+  int degree = 1;
+  double gamma = 1.0, coef0 = 0.0, nugget = 0.0;
+  const double* X = nullptr;
+  const double* nrm = nullptr;
+  const double* scale = nullptr;
+};
+void kernop_norms(int64_t n, int d4, const double* X, double* nrm, hipStream_t s);
+// U = Op Q for row-major n x b blocks (U must not alias Q), any b >= 1: column chunks of 32 and 16
+// on fp64 MFMA, the rest in chunks of <= 8 by the plain kernel.  Rows past n are not touched.
+// Fixed summation order, no atomics, no scratch.  false: bad shape (nothing launched).
+bool kernop_apply(const KernOp& op, const double* Q, int b, double* U, hipStream_t s);
+
 // --- tsmm.hip ----------------------------------------------------------------------------
 // Partial Gram: slab[s][a][c] = sum over rows of split s of W[r][a] * X[r][c]
 //   W: run of nW panels (a in [0, nW*w)), X: panels (c in [0, X.count*X.w)).

@@ -189,6 +189,11 @@ struct MatrixBufs : PanelBufs, SegTableBufs, TierBufs, RectShiftBufs, LowrankBuf
   // through d_rect_y (m x rect_y_cols)
   SegTierBuf rect_side[2];
   DevBuf<double> d_rect_y;
+  // implicit kernel matrix (rbl_set_matrix_kernel; kernelop.hip): the points row-major n x kern_d4
+  // (zero-padded columns), their squared norms, and the scale of rbl_set_kernel_scale (null: ones)
+  DevBuf<double> d_kern_x;
+  DevBuf<double> d_kern_nrm;
+  DevBuf<double> d_kern_scale;
 };
 
 // ---- buffers that live as long as one Krylov run (free_run)
@@ -295,6 +300,11 @@ struct rbl_ctx : rbl::api::MatrixBufs, rbl::api::RunBufs, rbl::api::CtxBufs {
   // rank-one shift C = B - u v^T (rbl_set_rect_shift): the operator is then C^T C
   bool rect_shift = false;
   int rect_ts_cols = 0;
+  // implicit kernel matrix over n points in kern_d dimensions (rbl_set_matrix_kernel): the operator
+  // is diag(s) K diag(s) + kern_nugget I, evaluated by kernelop.hip and never stored
+  bool kernop = false;
+  int kern_d = 0, kern_d4 = 0, kern_kind = 0, kern_degree = 0;
+  double kern_gamma = 0.0, kern_coef0 = 0.0, kern_nugget = 0.0;
   // implicit symmetric low-rank update (rbl_set_lowrank): the operator is A + P S P^T, applied
   // by apply_A after the SpMM
   int lr_r = 0, lr_rp = 0;
@@ -1577,7 +1587,26 @@ size_t gram_slab_elems(const rbl_ctx* ctx, int b, int max_blocks, int basis_bits
   return slab;
 }
 
-bool has_matrix(const rbl_ctx* ctx) { return ctx->d_rowptr || ctx->dense || ctx->rect; }
+bool has_matrix(const rbl_ctx* ctx) { return ctx->d_rowptr || ctx->dense || ctx->rect || ctx->kernop; }
+
+// the kernel matrix held as kernelop.hip takes it
+static_assert(RBL_KERNEL_RBF == kKernRbf && RBL_KERNEL_LAPLACE == kKernLaplace && RBL_KERNEL_POLY == kKernPoly &&
+                  RBL_KERNOP_MAX_DIM == kKernMaxDim,
+              "rbl_hip.h and kernels.hpp name the same kernels");
+KernOp kernop(const rbl_ctx* ctx) {
+  KernOp op;
+  op.n = ctx->n;
+  op.d4 = ctx->kern_d4;
+  op.kind = ctx->kern_kind;
+  op.degree = ctx->kern_degree;
+  op.gamma = ctx->kern_gamma;
+  op.coef0 = ctx->kern_coef0;
+  op.nugget = ctx->kern_nugget;
+  op.X = ctx->d_kern_x;
+  op.nrm = ctx->d_kern_nrm;
+  op.scale = ctx->d_kern_scale;
+  return op;
+}
 
 // one orientation of a rectangular B as the kernels take it (0: B's rows, 1: B^T's rows)
 CsrDev::Tier rect_tier(const rbl_ctx* ctx, int side) {
@@ -1685,6 +1714,15 @@ int apply_A_stored(rbl_ctx* ctx, const double* Qin, int64_t off, int b, double* 
     spmm_rect(rect_tier(ctx, 0), Q, b, ctx->d_rect_y, nullptr, nullptr, nullptr, ctx->stream);
     spmm_rect(rect_tier(ctx, 1), ctx->d_rect_y, b, U, Qprev, Bi, nullptr, ctx->stream);
     ctx->path_stats[RBL_PATH_SPMM] += 1;
+    return 0;
+  }
+  if (ctx->kernop) {  // K evaluated tile by tile from the points; the 3-term term as for a dense A
+    if (!kernop_apply(kernop(ctx), Qin + (0 - off) * b, b, U, ctx->stream))
+      return fail(ctx, RBL_ERR_INVALID, "internal: kernel-matrix apply: shape not served");
+    if (Qprev) {
+      transpose_small(Bi, smallp(ctx, S_BT), b, ctx->stream);
+      CHK(tsmm_checked(ctx, run1(Qprev, b), smallp(ctx, S_BT), b, pan1(U, b), -1.0, 1.0, nullptr));
+    }
     return 0;
   }
   if (ctx->csr_dropped && rbl_spmm_kernel_for(ctx, b) != 5)
@@ -2480,6 +2518,9 @@ void free_matrix(rbl_ctx* ctx) {
   ctx->arrow_kb = 0;  // a pending arrow step belongs to the operator its basis was built with
   ctx->rect = false;
   ctx->rect_m = 0;
+  ctx->kernop = false;
+  ctx->kern_d = ctx->kern_d4 = ctx->kern_kind = ctx->kern_degree = 0;
+  ctx->kern_gamma = ctx->kern_coef0 = ctx->kern_nugget = 0.0;
   ctx->qfull_cols = 0;
   ctx->dense = false;
   ctx->dense_panels = 0;
@@ -3197,6 +3238,121 @@ int rbl_set_matrix_normal(rbl_ctx* ctx, int64_t nrows, int64_t ncols, int64_t nn
   return setup_halo(ctx);
 }
 
+int rbl_set_matrix_kernel(rbl_ctx* ctx, int64_t n, int d, const double* X, int64_t ldx, int kind,
+                          double gamma, double coef0, int degree) {
+  if (!ctx || n < 1 || !X || ldx < n)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_kernel: bad arguments");
+  if (ctx->nranks > 1)  // before any collective: no rank waits for another
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_kernel: one rank only");
+  if (d < 1 || d > RBL_KERNOP_MAX_DIM)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_kernel: d must be in [1," +
+                                          std::to_string(RBL_KERNOP_MAX_DIM) + "]");
+  if (kind != RBL_KERNEL_RBF && kind != RBL_KERNEL_LAPLACE && kind != RBL_KERNEL_POLY)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_kernel: unknown kernel kind");
+  if (!std::isfinite(gamma) || gamma <= 0.0 || !std::isfinite(coef0))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_kernel: gamma must be finite and > 0, coef0 finite");
+  if (degree < 1 || degree > 8)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_kernel: degree must be in [1,8]");
+  const int d4 = 4 * ((d + 3) / 4);
+  if (n >= ((int64_t)1 << 40) / RBL_MAX_BLOCK)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_kernel: n too large");
+  // column-major host points -> row-major, zero-padded to d4 columns
+  std::vector<double> xr((size_t)n * d4, 0.0);
+  for (int k = 0; k < d; ++k)
+    for (int64_t i = 0; i < n; ++i) {
+      const double v = X[i + k * ldx];
+      if (!std::isfinite(v)) return fail(ctx, RBL_ERR_INVALID, "rbl_set_matrix_kernel: X has a non-finite entry");
+      xr[(size_t)i * d4 + k] = v;
+    }
+  HIPC(hipSetDevice(ctx->device));
+  free_run(ctx);
+  free_matrix(ctx);
+  ctx->bounds = {0, n};
+  ctx->n = n;
+  ctx->r0 = 0;
+  ctx->r1 = n;
+  ctx->nloc = n;
+  ctx->nnz = n * n;
+  ctx->kernop = true;
+  ctx->kern_d = d;
+  ctx->kern_d4 = d4;
+  ctx->kern_kind = kind;
+  ctx->kern_degree = degree;
+  ctx->kern_gamma = gamma;
+  ctx->kern_coef0 = coef0;
+  HIPC(ctx->d_kern_x.alloc((size_t)n * d4));
+  HIPC(ctx->d_kern_nrm.alloc((size_t)n));
+  HIPC(hipMemcpyAsync(ctx->d_kern_x, xr.data(), (size_t)n * d4 * sizeof(double), hipMemcpyHostToDevice,
+                      ctx->stream));
+  kernop_norms(n, d4, ctx->d_kern_x, ctx->d_kern_nrm, ctx->stream);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(ctx->stream));
+  ctx->need_lo.assign(1, 0);
+  ctx->need_hi.assign(1, 0);
+  return setup_halo(ctx);
+}
+
+int rbl_set_kernel_scale(rbl_ctx* ctx, const double* scale, double nugget) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (!ctx->kernop) return fail(ctx, RBL_ERR_STATE, "rbl_set_kernel_scale: no kernel matrix");
+  if (!std::isfinite(nugget)) return fail(ctx, RBL_ERR_INVALID, "rbl_set_kernel_scale: nugget must be finite");
+  for (int64_t i = 0; scale && i < ctx->n; ++i)
+    if (!std::isfinite(scale[i]))
+      return fail(ctx, RBL_ERR_INVALID, "rbl_set_kernel_scale: scale has a non-finite entry");
+  HIPC(hipSetDevice(ctx->device));
+  HIPC(hipStreamSynchronize(ctx->stream));  // steps in flight still read the old scale
+  if (!scale) {
+    ctx->d_kern_scale.reset();
+  } else {
+    if (!ctx->d_kern_scale) HIPC(ctx->d_kern_scale.alloc((size_t)ctx->n));
+    HIPC(hipMemcpy(ctx->d_kern_scale, scale, ctx->n * sizeof(double), hipMemcpyHostToDevice));
+  }
+  ctx->kern_nugget = nugget;
+  return RBL_OK;
+}
+
+int rbl_kernel_info(rbl_ctx* ctx, int64_t* n, int* d, int* kind, double* gamma, double* coef0, int* degree,
+                    int* has_scale, double* nugget) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (!ctx->kernop) return fail(ctx, RBL_ERR_STATE, "rbl_kernel_info: no kernel matrix");
+  if (n) *n = ctx->n;
+  if (d) *d = ctx->kern_d;
+  if (kind) *kind = ctx->kern_kind;
+  if (gamma) *gamma = ctx->kern_gamma;
+  if (coef0) *coef0 = ctx->kern_coef0;
+  if (degree) *degree = ctx->kern_degree;
+  if (has_scale) *has_scale = ctx->d_kern_scale ? 1 : 0;
+  if (nugget) *nugget = ctx->kern_nugget;
+  return RBL_OK;
+}
+
+int rbl_bench_kernel_pass(rbl_ctx* ctx, int b, int reps, double* ms) {
+  if (!ctx || b < 1 || b > RBL_MAX_BLOCK || reps < 1 || !ms)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kernel_pass: bad arguments");
+  if (!ctx->kernop) return fail(ctx, RBL_ERR_STATE, "rbl_bench_kernel_pass: no kernel matrix");
+  HIPC(hipSetDevice(ctx->device));
+  DevBuf<double> q, u;
+  HIPC(q.alloc((size_t)ctx->n * b));
+  HIPC(u.alloc((size_t)ctx->n * b));
+  randn_block(q, ctx->n, b, 0, 1, ctx->stream);
+  const KernOp op = kernop(ctx);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  int st = RBL_OK;
+  kernop_apply(op, q, b, u, ctx->stream);  // warm-up
+  if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+  for (int r = 0; r < reps; ++r) kernop_apply(op, q, b, u, ctx->stream);
+  if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+  float t = 0.f;
+  if (hipEventElapsedTime(&t, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+  *ms = (double)t / reps;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_kernel_pass: a HIP call failed");
+  return RBL_OK;
+}
+
 int rbl_rect_info(rbl_ctx* ctx, int64_t* nrows, int64_t* ncols, int64_t* nnz) {
   if (!ctx) return RBL_ERR_INVALID;
   if (!ctx->rect) return fail(ctx, RBL_ERR_STATE, "rbl_rect_info: no rectangular matrix");
@@ -3342,6 +3498,7 @@ int rbl_get_matrix_csr(rbl_ctx* ctx, int64_t* rowptr, int32_t* colind, double* v
     return fail(ctx, RBL_ERR_STATE, "rbl_get_matrix_csr: the CSR was released (RBL_OPT_KEEP_CSR = 0)");
   if (!ctx || !ctx->d_rowptr)
     return fail(ctx, RBL_ERR_STATE, ctx && ctx->dense  ? "dense matrix: no CSR"
+                                    : ctx && ctx->kernop ? "kernel matrix: no CSR"
                                     : ctx && ctx->rect ? "rectangular matrix: use rbl_get_matrix_rect"
                                                        : "no matrix");
   HIPC(hipSetDevice(ctx->device));
@@ -3358,6 +3515,7 @@ int rbl_spmm_kernel_for(rbl_ctx* ctx, int b) {
   if (!ctx || !has_matrix(ctx)) return RBL_ERR_INVALID;
   if (ctx->dense) return 4;
   if (ctx->rect) return 8;
+  if (ctx->kernop) return RBL_SPMM_KERNEL_KERNOP;
   if (ctx->spmm_variant == 1) return 1;
   const int v = ctx->spmm_variant;
   const bool band = ctx->ntiles > 0 && ((b == 16 && ctx->band_ok16) || (b == 32 && ctx->band_ok32));
@@ -3375,6 +3533,7 @@ int rbl_matrix_format(rbl_ctx* ctx) {
   if (!ctx || !has_matrix(ctx)) return RBL_ERR_INVALID;
   if (ctx->dense) return 4;
   if (ctx->rect) return 5;
+  if (ctx->kernop) return RBL_MATRIX_FORMAT_KERNOP;
   if (ctx->d_bth) return 3;
   if (ctx->d_btp_hdr) return 2;
   if (ctx->d_bt) return 1;
@@ -3442,6 +3601,9 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   if (ctx->rect && basis_bits != 64)
     return fail(ctx, RBL_ERR_INVALID, "rbl_start: a rectangular B (rbl_set_matrix_normal) needs the "
                                       "fp64 basis (basis_bits = 64)");
+  if (ctx->kernop && basis_bits != 64)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_start: a kernel matrix (rbl_set_matrix_kernel) needs the fp64 "
+                                      "basis (basis_bits = 64)");
   if (ctx->filt_deg > 0 && basis_bits != 64)
     return fail(ctx, RBL_ERR_INVALID, "rbl_start: a Chebyshev filter (rbl_set_filter) needs the fp64 "
                                       "basis (basis_bits = 64)");

@@ -12,7 +12,9 @@ square-A drivers takes ``update=(P, S)`` for the implicit operator A + P S P^T (
 ``modularity_update``, ``deflation_update``, ``centering_update``, ``RBL_modularity``);
 ``apply_function`` / ``trace_function`` / ``diag_function`` (``rbl.funm``) give f(A) B, tr f(A) and
 diag f(A) by Chebyshev series (``heat_kernel_signature``, ``subgraph_centrality``, ``local_density``,
-``logdet``); ``Context`` wraps the C-ABI of
+``logdet``); a ``KernelMatrix(X, kind, gamma)`` (``rbl.kernelop``) is the implicit kernel matrix over
+the rows of X as the A of any of these (``RBL_kernel_pca``, ``RBL_spectral_embedding``,
+``kernel_centering_update``); ``Context`` wraps the C-ABI of
 librbl_hip.so (include/rbl_hip.h).  Importing this package loads the HIP library and fails
 loudly if it has not been built: there is no CPU fallback.
 """
@@ -32,5 +34,7 @@ from .density import (RBL_interval, check_moments, eig_count, interval_degree, i
                       jackson, kpm_count, kpm_density, spectral_density)
 from .lowrank import (RBL_modularity, centering_update, deflation_update,  # noqa: F401
                       modularity_update)
+from .kernelop import (KernelMatrix, RBL_kernel_pca, RBL_spectral_embedding,  # noqa: F401
+                       kernel_centering_update, row_normalize)
 from .funm import (DiagResult, apply_function, cheb_coeffs, cheb_fit, diag_function, diag_series,  # noqa: F401
                    heat_kernel_signature, local_density, logdet, subgraph_centrality, trace_function)

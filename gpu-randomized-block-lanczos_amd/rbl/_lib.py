@@ -48,6 +48,14 @@ RBL_BUILD_VARIANTS = 1
 # a rectangular B (rbl_set_matrix_normal): what rbl_spmm_kernel_for / rbl_matrix_format report
 RBL_SPMM_KERNEL_RECT = 8
 RBL_MATRIX_FORMAT_RECT = 5
+# an implicit kernel matrix (rbl_set_matrix_kernel): the kernels, the largest d, and what
+# rbl_spmm_kernel_for / rbl_matrix_format report
+RBL_KERNEL_RBF = 0
+RBL_KERNEL_LAPLACE = 1
+RBL_KERNEL_POLY = 2
+RBL_KERNOP_MAX_DIM = 256
+RBL_SPMM_KERNEL_KERNOP = 9
+RBL_MATRIX_FORMAT_KERNOP = 6
 # rbl_cheb_diag: the block drawn when X is NULL
 RBL_PROBE_GAUSS = 0
 RBL_PROBE_SIGN = 1
@@ -90,6 +98,12 @@ SIGNATURES = {
     "rbl_set_rect_shift": (C.c_int, [_p, _pd, _pd]),
     "rbl_get_rect_shift": (C.c_int, [_p, _pd, _pd]),
     "rbl_apply_rect_shifted": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd]),
+    "rbl_set_matrix_kernel": (C.c_int, [_p, _i64, C.c_int, _pd, _i64, C.c_int, C.c_double, C.c_double,
+                                        C.c_int]),
+    "rbl_set_kernel_scale": (C.c_int, [_p, _pd, C.c_double]),
+    "rbl_kernel_info": (C.c_int, [_p, _pi64, C.POINTER(C.c_int), C.POINTER(C.c_int), _pd, _pd,
+                                  C.POINTER(C.c_int), C.POINTER(C.c_int), _pd]),
+    "rbl_bench_kernel_pass": (C.c_int, [_p, C.c_int, C.c_int, _pd]),
     "rbl_gen_matrix_hashwindow": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_circuit": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_rmat": (C.c_int, [_p, _i64, C.c_int, _i64, C.c_double, C.c_double, C.c_double,

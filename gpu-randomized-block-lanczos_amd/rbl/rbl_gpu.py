@@ -119,7 +119,14 @@ class Context:
         the rows of the even split).  The sparse arrays passed are A's rows (CSR): for the
         symmetric A of RBL_gpu.jl:209 they are exactly Julia's SparseMatrixCSC arrays; for any
         other A the device then computes A Q, as cuSPARSE does on the CSC matrix (benchmark.jl:58
-        runs an unsymmetric sprandn) and as julia/RBL_hip.jl does by transposing first."""
+        runs an unsymmetric sprandn) and as julia/RBL_hip.jl does by transposing first.
+        A ``rbl.kernelop.KernelMatrix`` uploads its points, scale and nugget (set_matrix_kernel)."""
+        from .kernelop import KernelMatrix
+        if isinstance(A, KernelMatrix):
+            self.set_matrix_kernel(A.X, A.kind, A.gamma, A.coef0, A.degree)
+            if A.scale is not None or A.nugget != 0.0:
+                self.set_kernel_scale(A.scale, A.nugget)
+            return
         if isinstance(A, np.ndarray):
             n = A.shape[0]
             if A.ndim != 2 or A.shape[1] != n:
@@ -237,6 +244,56 @@ class Context:
         self._check(lib.rbl_apply_rect_shifted(self._h, int(bool(trans)), X.shape[1], dptr(X),
                                                dptr(Y)), "rbl_apply_rect_shifted")
         return Y
+
+    # -- implicit kernel matrix: K_ij = kappa(x_i, x_j) from the points alone -----------------
+    def set_matrix_kernel(self, X, kind="rbf", gamma: float = 1.0, coef0: float = 0.0,
+                          degree: int = 3) -> None:
+        """The kernel matrix over the rows of X (n x d) as the operator (rbl_set_matrix_kernel):
+        kind "rbf" exp(-gamma |x-y|^2), "laplace" exp(-gamma |x-y|), "poly" (gamma x^T y +
+        coef0)^degree, or the RBL_KERNEL_* id.  K is never formed.  One rank, fp64 basis."""
+        from .kernelop import KINDS
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2 or X.shape[0] < 1:
+            raise ValueError("set_matrix_kernel: X must be an n x d array with n >= 1")
+        if isinstance(kind, str):
+            if kind not in KINDS:
+                raise ValueError("set_matrix_kernel: kind must be 'rbf', 'laplace' or 'poly'")
+            kind = KINDS[kind]
+        X = np.asfortranarray(X)
+        n, d = X.shape
+        self._check(lib.rbl_set_matrix_kernel(self._h, n, d, dptr(X), n, int(kind), float(gamma),
+                                              float(coef0), int(degree)), "rbl_set_matrix_kernel")
+
+    def set_kernel_scale(self, scale=None, nugget: float = 0.0) -> None:
+        """The operator becomes diag(scale) K diag(scale) + nugget I for the kernel matrix held
+        (rbl_set_kernel_scale); ``None, 0.0`` clears both."""
+        if scale is not None:
+            scale = np.ascontiguousarray(scale, dtype=np.float64).ravel()
+            if scale.size != self.kernel_info()["n"]:
+                raise ValueError(f"set_kernel_scale: scale must have n = {self.kernel_info()['n']} entries")
+        self._check(lib.rbl_set_kernel_scale(self._h, dptr(scale), float(nugget)), "rbl_set_kernel_scale")
+
+    def kernel_info(self) -> dict:
+        """n, d, kind (RBL_KERNEL_*), gamma, coef0, degree, has_scale and nugget of the kernel
+        matrix held (rbl_kernel_info); RBLError (RBL_ERR_STATE) when the matrix is of another kind."""
+        import ctypes as C
+        n = C.c_int64(0)
+        d, kind, degree, has = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        g, c0, nug = np.zeros(1), np.zeros(1), np.zeros(1)
+        self._check(lib.rbl_kernel_info(self._h, C.byref(n), C.byref(d), C.byref(kind), dptr(g), dptr(c0),
+                                        C.byref(degree), C.byref(has), dptr(nug)), "rbl_kernel_info")
+        return {"n": n.value, "d": d.value, "kind": kind.value, "gamma": float(g[0]),
+                "coef0": float(c0[0]), "degree": degree.value, "has_scale": bool(has.value),
+                "nugget": float(nug[0])}
+
+    def bench_kernel_pass(self, b: int, reps: int = 5) -> float:
+        """Milliseconds per application of the kernel matrix held to a device-resident block of b
+        columns (rbl_bench_kernel_pass)."""
+        ms = np.zeros(1)
+        self._check(lib.rbl_bench_kernel_pass(self._h, int(b), int(reps), dptr(ms)), "rbl_bench_kernel_pass")
+        return float(ms[0])
 
     # -- implicit symmetric low-rank update: the operator A + P S P^T ------------------------
     def set_lowrank(self, P, S) -> None:
@@ -672,9 +729,12 @@ def rccl_version() -> dict:
 
 def set_update(ctx: Context, update) -> None:
     """The ``update=(P, S)`` keyword of the drivers: the operator A + P S P^T, set straight after
-    the matrix (so bound estimation sees the updated operator); None: the plain A."""
+    the matrix (so bound estimation sees the updated operator); None: the plain A.  A callable is
+    called with the loaded context and returns the pair (``rbl.kernelop.kernel_centering_update``)."""
     if update is None:
         return
+    if callable(update):
+        update = update(ctx)
     try:
         P, S = update
     except (TypeError, ValueError):

@@ -196,8 +196,10 @@ def RBL_thick(A, k: int, b: int, *, max_blocks: int, keep_blocks=None, update=No
     never formed (Context.set_lowrank; rbl.lowrank builds the usual ones).  A run that does not
     converge within max_restarts restarts returns its last Ritz pairs with info.converged False
     and status RBL_WARN_NOT_CONVERGED."""
-    if not (sp.issparse(A) or isinstance(A, np.ndarray)) or A.ndim != 2 or A.shape[0] != A.shape[1]:
-        raise ValueError("RBL_thick: A must be a square SciPy sparse matrix or dense array")
+    from .kernelop import KernelMatrix
+    if (not (sp.issparse(A) or isinstance(A, (np.ndarray, KernelMatrix))) or A.ndim != 2 or
+            A.shape[0] != A.shape[1]):
+        raise ValueError("RBL_thick: A must be a square SciPy sparse matrix, dense array or KernelMatrix")
     check_keep_blocks(k, b, max_blocks, keep_blocks)
     if k > A.shape[0]:
         raise ValueError(f"RBL_thick: k = {k} exceeds n = {A.shape[0]}")

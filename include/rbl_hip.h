@@ -282,6 +282,48 @@ int rbl_get_rect_shift(rbl_ctx* ctx, double* u_out, double* v_out);
  * Without a shift it equals rbl_apply_rect bit for bit.  b <= RBL_MAX_BLOCK; timed under "AQ"
  * (the reduction included) while RBL_OPT_TIMERS is set. */
 int rbl_apply_rect_shifted(rbl_ctx* ctx, int trans, int b, const double* X, double* Y);
+/* Implicit kernel matrix over n points in d dimensions (X: n x d column-major, leading dimension
+ * ldx >= n; copied, the caller's array is not kept):
+ *     Op = diag(s) K diag(s) + nugget I,    K_ij = kappa(x_i, x_j),
+ *   RBL_KERNEL_RBF      exp(-gamma |x - y|^2)
+ *   RBL_KERNEL_LAPLACE  exp(-gamma |x - y|_2)
+ *   RBL_KERNEL_POLY     (gamma x^T y + coef0)^degree
+ * K is never formed: the device keeps the n x 4 ceil(d / 4) points and their squared norms, and
+ * every product Op Q evaluates K tile by tile on fp64 MFMA (column chunks of 32 and 16; what is
+ * left of any other width by a plain kernel), O(n^2 (d + b)) flops on O(n (d + b)) bytes.
+ * Distances are taken in Gram form |x_i|^2 + |x_j|^2 - 2 x_i^T x_j, clamped at 0 and set to 0 on
+ * the diagonal, so K_ii = 1 exactly for the two radial kernels (mean-centre the points first: the
+ * cancellation grows with their norms); K is symmetric bit for bit.  Fixed summation order, no
+ * atomics: two applications give the same bits.  gamma finite and > 0, coef0 finite, 1 <= degree
+ * <= 8 (checked for every kind; coef0 and degree are used by RBL_KERNEL_POLY only), 1 <= d <=
+ * RBL_KERNOP_MAX_DIM, X finite — else RBL_ERR_INVALID, the context unchanged.
+ * Afterwards: rbl_matrix_info reports n, rows [0, n), nnz_local = n^2; rbl_apply, rbl_start /
+ * rbl_step / rbl_ritz, the restarted and thick-restarted entry points, the Chebyshev filters,
+ * series, moments and diagonal, and rbl_set_lowrank run on Op; rbl_spmm_kernel_for reports
+ * RBL_SPMM_KERNEL_KERNOP for every b and rbl_matrix_format RBL_MATRIX_FORMAT_KERNOP;
+ * rbl_get_matrix_csr fails (RBL_ERR_STATE).  Setting any matrix clears it, its scale and nugget.
+ * Limits: one rank only — on a context with nranks > 1 this returns RBL_ERR_INVALID before any
+ * collective; the fp64 basis only — rbl_start with basis_bits = 32 returns RBL_ERR_INVALID. */
+#define RBL_KERNEL_RBF      0
+#define RBL_KERNEL_LAPLACE  1
+#define RBL_KERNEL_POLY     2
+#define RBL_KERNOP_MAX_DIM  256
+#define RBL_SPMM_KERNEL_KERNOP   9   /* rbl_spmm_kernel_for with a kernel matrix */
+#define RBL_MATRIX_FORMAT_KERNOP 6   /* rbl_matrix_format with a kernel matrix   */
+int rbl_set_matrix_kernel(rbl_ctx* ctx, int64_t n, int d, const double* X, int64_t ldx, int kind,
+                          double gamma, double coef0, int degree);
+/* The scale s (n entries, copied; NULL: all ones, nothing stored) and the nugget of the kernel
+ * matrix held: s = deg^-1/2 gives the normalised affinity D^-1/2 K D^-1/2, the nugget K + tau I.
+ * A run in flight is waited for.  (NULL, 0) returns to the bits of a context that never had them.
+ * RBL_ERR_STATE without a kernel matrix; RBL_ERR_INVALID for a non-finite entry or nugget — the
+ * context and an earlier scale stay as they were. */
+int rbl_set_kernel_scale(rbl_ctx* ctx, const double* scale, double nugget);
+/* What the kernel matrix held was set with (any pointer may be NULL); RBL_ERR_STATE without one. */
+int rbl_kernel_info(rbl_ctx* ctx, int64_t* n, int* d, int* kind, double* gamma, double* coef0,
+                    int* degree, int* has_scale, double* nugget);
+/* Milliseconds per application of the kernel matrix held to a device-resident N(0,1) block of b
+ * columns: one warm-up pass, then `reps` passes between two hipEvents.  RBL_ERR_STATE without one. */
+int rbl_bench_kernel_pass(rbl_ctx* ctx, int b, int reps, double* ms);
 int rbl_gen_matrix_hashwindow(rbl_ctx* ctx, int64_t n, int64_t halfwidth, double density,
                               uint64_t seed, int nplant, const double* plant);
 /* Device-side generator of the seeded symmetric R-MAT matrix (BASELINE
@@ -318,13 +360,15 @@ int rbl_apply(rbl_ctx* ctx, int b, const double* X, double* Y);
  * 1 = global-gather CSR, 2 = LDS-window CSR (DPP), 3 = LDS-densified band on fp64 MFMA,
  * 4 = dense panel GEMM (rbl_set_matrix_dense), 5 = band-tile format on fp64 MFMA,
  * 6 = segmented gather (unstructured patterns, b in {16, 32}), 7 = column panels,
- * 8 = rectangular gather pair (rbl_set_matrix_normal, every b). */
+ * 8 = rectangular gather pair (rbl_set_matrix_normal, every b),
+ * 9 = implicit kernel matrix (rbl_set_matrix_kernel, every b). */
 int rbl_spmm_kernel_for(rbl_ctx* ctx, int b);
 /* The device format the matrix is held in: 0 = CSR only, 1 = band tiles (16 x (16 + 2H)
  * doubles), 2 = packed band tiles (RBL_BT_PACK=1), 3 = half band tiles (A symmetric bit for
  * bit: diagonal block + right strip, the left part transposed back in the kernel, same
  * results as 1; opt-in with RBL_BT_HALF=1), 4 = dense panels, 5 = rectangular B as two CSRs
- * (B and B^T, rbl_set_matrix_normal). */
+ * (B and B^T, rbl_set_matrix_normal), 6 = the points of an implicit kernel matrix
+ * (rbl_set_matrix_kernel). */
 int rbl_matrix_format(rbl_ctx* ctx);
 
 /* ---- Krylov run -----------------------------------------------------------------------

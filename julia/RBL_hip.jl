@@ -100,6 +100,41 @@ function set_lowrank!(ctx, P::Matrix{Float64}, S::Matrix{Float64})
                          ctx, Cint(size(P, 2)), P, S), "rbl_set_lowrank")
 end
 
+# An implicit kernel matrix over the n rows of X (n x d): diag(scale) K diag(scale) + nugget I with
+# K_ij = kappa(x_i, x_j); kind :rbf exp(-gamma |x-y|^2), :laplace exp(-gamma |x-y|), :poly
+# (gamma x'y + coef0)^degree.  Only the points go to the device (rbl_set_matrix_kernel); K is
+# evaluated tile by tile in every product and never formed.  One rank, fp64 basis.
+struct KernelPoints
+    X::Matrix{Float64}
+    kind::Symbol
+    gamma::Float64
+    coef0::Float64
+    degree::Int
+    scale::Union{Nothing,Vector{Float64}}
+    nugget::Float64
+end
+KernelPoints(X::Matrix{Float64}; kind::Symbol = :rbf, gamma::Float64 = 1.0, coef0::Float64 = 0.0,
+             degree::Int = 3, scale = nothing, nugget::Float64 = 0.0) =
+    KernelPoints(X, kind, gamma, coef0, degree, scale, nugget)
+Base.size(K::KernelPoints) = (size(K.X, 1), size(K.X, 1))
+Base.size(K::KernelPoints, i::Int) = size(K.X, 1)
+const RBL_KERNEL_IDS = Dict(:rbf => Cint(0), :laplace => Cint(1), :poly => Cint(2))
+
+function set_matrix!(ctx, K::KernelPoints)
+    haskey(RBL_KERNEL_IDS, K.kind) || throw(ArgumentError("KernelPoints: kind must be :rbf, :laplace or :poly"))
+    rbl_check(ctx, ccall((:rbl_set_matrix_kernel, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Int64, Cint, Ptr{Float64}, Int64, Cint, Cdouble, Cdouble, Cint),
+                         ctx, size(K.X, 1), Cint(size(K.X, 2)), K.X, size(K.X, 1), RBL_KERNEL_IDS[K.kind],
+                         K.gamma, K.coef0, Cint(K.degree)), "rbl_set_matrix_kernel")
+    if K.scale !== nothing || K.nugget != 0.0
+        K.scale === nothing || length(K.scale) == size(K.X, 1) ||
+            throw(ArgumentError("KernelPoints: scale must have one entry per point"))
+        rbl_check(ctx, ccall((:rbl_set_kernel_scale, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Ptr{Float64}, Cdouble),
+                             ctx, K.scale === nothing ? C_NULL : K.scale, K.nugget), "rbl_set_kernel_scale")
+    end
+end
+
 function rbl_context(device::Int)
     hr = Ref{Ptr{Cvoid}}(C_NULL)
     st = ccall((:rbl_create, librbl_hip), Cint, (Ref{Ptr{Cvoid}}, Cint), hr, Cint(device))
@@ -132,7 +167,7 @@ function fold_device_timers!(to, ctx::Ptr{Cvoid})
     end
 end
 
-function RBL_hip(A::Union{SparseMatrixCSC{Float64},Matrix{Float64}}, k::Int64, b::Int64;
+function RBL_hip(A::Union{SparseMatrixCSC{Float64},Matrix{Float64},KernelPoints}, k::Int64, b::Int64;
                  device::Int = 0, seed::UInt64 = rand(UInt64), kryl_sz::Int64 = 1200,
                  basis_bits::Int = (FLOAT == Float32 ? 32 : 64), device_blocks::Int = 0,
                  timer = nothing, normal::Bool = false, shift = nothing, update = nothing)
@@ -276,6 +311,18 @@ end
 function RBL_gpu(A::Union{SparseMatrixCSC{DOUBLE},Matrix{DOUBLE}}, k::Int64, b::Int64)
     timer = isdefined(Main, :to) ? Main.to : nothing
     return RBL_hip(A, k, b; timer = timer)
+end
+
+# The k eigenpairs of largest |lambda| of the kernel matrix over the rows of X (n x d), from the
+# points alone: RBL_hip on KernelPoints(X; kind, gamma, coef0, degree, scale, nugget).  With
+# scale = deg .^ -0.5 (deg = K 1) it is the normalised affinity of spectral clustering; update =
+# (P, S) adds a low-rank term (kernel PCA's centring: P = [1 K1/n], S = [c -1; -1 0]).
+function RBL_gpu_kernel(X::Matrix{Float64}, k::Int64, b::Int64; kind::Symbol = :rbf,
+                        gamma::Float64 = 1.0, coef0::Float64 = 0.0, degree::Int = 3, scale = nothing,
+                        nugget::Float64 = 0.0, seed::UInt64 = rand(UInt64), update = nothing)
+    timer = isdefined(Main, :to) ? Main.to : nothing
+    K = KernelPoints(X, kind, gamma, coef0, degree, scale, nugget)
+    return RBL_hip(K, k, b; timer = timer, basis_bits = 64, seed = seed, update = update)
 end
 
 # Drop-in for images.jl:29-33 on a sparse rectangular B: `D, V = RBL_gpu(transpose(B)*B, k, b)`,

@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""One application of the implicit kernel matrix (kernelop.hip) at the shapes of DESIGN section 16,
+and the stored route to the same product.
+
+Implicit: rbl_bench_kernel_pass (hipEvents around `--reps` passes after one warm-up, a
+device-resident N(0,1) block) for each (n, d, b) of --shapes, rbf kernel on three-blob points;
+`--rounds` rounds, the shapes alternating within a round; the median, and from it pair
+evaluations per second (n^2 / t) and the MFMA rate by the flop model n^2 (2 d4 + 2 b) / t.
+Stored: K materialised on the host at n = --dense-n (0: skipped), rbl_set_matrix_dense, and the
+wall time of the same Context.apply (host block in, host block out) for both operators at
+b = --dense-b, `--rounds` rounds of `--reps` calls, median per call — the host transfers are in
+both numbers.
+
+Writes one JSON document (default profiles/kernelop_bench.json)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "gpu-randomized-block-lanczos_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def points(n, d, seed=0):
+    rng = np.random.default_rng(seed)
+    centres = 3.0 * rng.standard_normal((3, d)) / np.sqrt(d)
+    X = centres[np.arange(n) % 3] + 2.0 * rng.standard_normal((n, d)) / np.sqrt(d)
+    return np.asfortranarray(X - X.mean(axis=0))
+
+
+def materialise(X, gamma, rows=2048):
+    """The rbf kernel matrix of X, column-major, built in column blocks (K is symmetric)."""
+    n = X.shape[0]
+    nrm = (X * X).sum(axis=1)
+    K = np.empty((n, n), order="F")
+    for c0 in range(0, n, rows):
+        c1 = min(n, c0 + rows)
+        blk = X[c0:c1] @ X.T                                    # rows c0..c1 of X X^T
+        blk *= -2.0
+        blk += nrm[c0:c1, None]
+        blk += nrm[None, :]
+        np.maximum(blk, 0.0, out=blk)
+        blk *= -gamma
+        np.exp(blk, out=blk)
+        K[:, c0:c1] = blk.T
+    K[np.diag_indices(n)] = 1.0
+    return K
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", type=int, nargs="+",
+                    default=[32768, 16, 32, 32768, 128, 32, 32768, 16, 16, 131072, 16, 32],
+                    help="n d b triples")
+    ap.add_argument("--gamma", type=float, default=0.5)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--dense-n", type=int, default=32768)
+    ap.add_argument("--dense-d", type=int, default=16)
+    ap.add_argument("--dense-b", type=int, default=32)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kernelop_bench.json"))
+    args = ap.parse_args()
+    if len(args.shapes) % 3:
+        ap.error("--shapes takes n d b triples")
+    shapes = [tuple(args.shapes[i:i + 3]) for i in range(0, len(args.shapes), 3)]
+
+    import rbl
+
+    doc = {"kernel": "rbf", "gamma": args.gamma, "reps": args.reps, "rounds": args.rounds, "implicit": []}
+    ctxs = {}
+    try:
+        for n, d, b in shapes:                                    # one context per point set
+            if (n, d) not in ctxs:
+                c = rbl.Context(0)
+                c.set_matrix_kernel(points(n, d), "rbf", args.gamma)
+                ctxs[(n, d)] = c
+            ctxs[(n, d)].bench_kernel_pass(b, 1)                  # warm every shape once
+        times = {s: [] for s in shapes}
+        for _ in range(args.rounds):
+            for s in shapes:
+                times[s].append(ctxs[s[:2]].bench_kernel_pass(s[2], args.reps))
+        for n, d, b in shapes:
+            ms = statistics.median(times[(n, d, b)])
+            d4 = 4 * ((d + 3) // 4)
+            row = {"n": n, "d": d, "b": b, "ms": ms, "ms_rounds": times[(n, d, b)],
+                   "pairs_per_s": n * n / (ms * 1e-3),
+                   "mfma_tflops_by_model": n * n * (2 * d4 + 2 * b) / (ms * 1e-3) / 1e12,
+                   "stored_fp64_bytes": 8 * n * n}
+            doc["implicit"].append(row)
+            print(json.dumps(row), flush=True)
+    finally:
+        for c in ctxs.values():
+            c.close()
+
+    if args.dense_n > 0:
+        n, d, b = args.dense_n, args.dense_d, args.dense_b
+        X = points(n, d)
+        Q = np.asfortranarray(np.random.default_rng(1).standard_normal((n, b)))
+
+        def wall(ctx):
+            ctx.apply(Q)                                          # warm-up
+            out = []
+            for _ in range(args.rounds):
+                t0 = time.perf_counter()
+                for _ in range(args.reps):
+                    Y = ctx.apply(Q)
+                out.append((time.perf_counter() - t0) * 1e3 / args.reps)
+            return statistics.median(out), out, Y
+
+        with rbl.Context(0) as ctx:
+            ctx.set_matrix_kernel(X, "rbf", args.gamma)
+            k_ms, k_all, Yk = wall(ctx)
+            k_dev = ctx.bench_kernel_pass(b, args.reps)
+        t0 = time.perf_counter()
+        K = materialise(X, args.gamma)
+        form_s = time.perf_counter() - t0
+        with rbl.Context(0) as ctx:
+            t0 = time.perf_counter()
+            ctx.set_matrix(K)
+            upload_s = time.perf_counter() - t0
+            d_ms, d_all, Yd = wall(ctx)
+        doc["stored"] = {"n": n, "d": d, "b": b, "stored_bytes": 8 * n * n, "host_form_s": form_s,
+                         "upload_s": upload_s, "apply_wall_ms_dense": d_ms, "apply_wall_ms_dense_rounds": d_all,
+                         "apply_wall_ms_implicit": k_ms, "apply_wall_ms_implicit_rounds": k_all,
+                         "implicit_device_ms": k_dev, "implicit_over_dense": k_ms / d_ms,
+                         "max_rel_difference": float(np.abs(Yk - Yd).max() / np.abs(Yd).max())}
+        print(json.dumps(doc["stored"]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
