@@ -35,27 +35,15 @@
 // <= 8 with leading dimension b (the kernel matrix is re-evaluated per chunk).
 #include <algorithm>
 
+#include "kernelop_dev.hpp"
 #include "kernels.hpp"
 
 namespace rbl {
 
 namespace {
 
-typedef double d4v __attribute__((ext_vector_type(4)));
-
-template <int KIND>
-__device__ __forceinline__ double kern_value(double gamma, double coef0, int degree, double ni, double nj,
-                                              double p, bool same) {
-  if constexpr (KIND == kKernPoly) {
-    const double t = fma(gamma, p, coef0);
-    double r = t;
-    for (int q = 1; q < degree; ++q) r *= t;
-    return r;
-  }
-  double d2 = fmax((ni + nj) - 2.0 * p, 0.0);
-  if (same) d2 = 0.0;
-  return exp(-gamma * (KIND == kKernRbf ? d2 : sqrt(d2)));
-}
+// kern_value, kern_jt and kern_lds_doubles are shared with the cross-kernel product
+using namespace kerndev;
 
 __global__ __launch_bounds__(256) void k_kernop_norms(int64_t n, int d4, const double* __restrict__ X,
                                                       double* __restrict__ nrm) {
@@ -67,12 +55,6 @@ __global__ __launch_bounds__(256) void k_kernop_norms(int64_t n, int d4, const d
     s = fma(x, x, s);
   }
   nrm[i] = s;
-}
-
-// column points per stage: 4 KS JT doubles of X and 16 NB JT of Q per buffer
-constexpr int kern_jt(int KS) { return KS <= 4 ? 64 : KS <= 16 ? 32 : 16; }
-constexpr int kern_lds_doubles(int KS, int NB) {
-  return 2 * (4 * KS * (kern_jt(KS) + 1) + kern_jt(KS) * 16 * NB + kern_jt(KS));
 }
 
 // KS: the k steps (of 4 columns) the X_i fragment has room for, ks <= KS of them used (ks == KS, d4

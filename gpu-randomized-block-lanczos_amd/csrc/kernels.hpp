@@ -395,6 +395,37 @@ void kernop_norms(int64_t n, int d4, const double* X, double* nrm, hipStream_t s
 // Fixed summation order, no atomics, no scratch.  false: bad shape (nothing launched).
 bool kernop_apply(const KernOp& op, const double* Q, int b, double* U, hipStream_t s);
 
+// --- kernelop_cross.hip: the rectangular cross-kernel product (rbl_kernel_cross) ------------------
+// Y = diag(sr) kappa(R, C) diag(sc) W: R mr x d4 row points, C mc x d4 column points (both as X
+// above, norms from kernop_norms), W mc x b and Y mr x b row-major with leading dimension b.  sr / sc
+// null: all ones.  No diagonal rule and no nugget.
+struct KernCross {
+  int64_t mr = 0, mc = 0;
+  int d4 = 0;
+  int kind = kKernRbf;
+  int degree = 1;
+  double gamma = 1.0, coef0 = 0.0;
+  const double* R = nullptr;
+  const double* rnrm = nullptr;
+  const double* C = nullptr;
+  const double* cnrm = nullptr;
+  const double* sr = nullptr;
+  const double* sc = nullptr;
+};
+// The split of the column range, a function of the shapes alone (never of the device, so the bits do
+// not depend on the CU count): the fewest splits that bring ceil(mr / 64) x S to kKernCrossWorkgroups
+// workgroups, at most kKernCrossMaxSplits, and no split shorter than kKernCrossMinStages stages of
+// kern_jt column points (so never more splits than stages); 1 when the rows alone reach the target.
+constexpr int kKernCrossWorkgroups = 512, kKernCrossMaxSplits = 64, kKernCrossMinStages = 4;
+int kernop_cross_splits(int64_t mr, int64_t mc, int d4);
+// Any b >= 1 on fp64 MFMA (column chunks of 32, 16 and a zero-padded last chunk).  splits = 1: the
+// main kernel writes Y, part is not used.  splits > 1 (<= kKernCrossMaxSplits and <= the stages of
+// the column range): part holds splits x mr x b doubles; the partials are added in ascending split
+// order by one owner thread per output.  Fixed summation order, no atomics.  false: bad shape
+// (nothing launched).
+bool kernop_cross(const KernCross& op, const double* W, int b, double* Y, double* part, int splits,
+                  hipStream_t s);
+
 // --- tsmm.hip ----------------------------------------------------------------------------
 // Partial Gram: slab[s][a][c] = sum over rows of split s of W[r][a] * X[r][c]
 //   W: run of nW panels (a in [0, nW*w)), X: panels (c in [0, X.count*X.w)).

@@ -3353,6 +3353,138 @@ int rbl_bench_kernel_pass(rbl_ctx* ctx, int b, int reps, double* ms) {
   return RBL_OK;
 }
 
+namespace {
+// The buffers of one cross-kernel product (rbl_kernel_cross, rbl_bench_kernel_cross): they live as
+// long as the call — the new points row-major m x d4 with their norms, the two blocks, and the
+// S x rows x b partials of a split column range (empty when S = 1).
+struct CrossBufs {
+  DevBuf<double> z, znrm, w, wr, y, part;
+};
+
+// Z (m x d, column-major, ldz) -> row-major m x d4 zero-padded; false at a non-finite entry
+bool cross_points(int64_t m, int d, int d4, const double* Z, int64_t ldz, std::vector<double>& zr) {
+  zr.assign((size_t)m * d4, 0.0);
+  for (int k = 0; k < d; ++k)
+    for (int64_t i = 0; i < m; ++i) {
+      const double v = Z[i + k * ldz];
+      if (!std::isfinite(v)) return false;
+      zr[(size_t)i * d4 + k] = v;
+    }
+  return true;
+}
+
+// the product of the kernel matrix held with the m uploaded points B.z: trans = 0 kappa(Z, X) diag(s),
+// trans = 1 diag(s) kappa(X, Z)
+KernCross cross_op(const rbl_ctx* ctx, const CrossBufs& B, int64_t m, int trans) {
+  KernCross op;
+  op.d4 = ctx->kern_d4;
+  op.kind = ctx->kern_kind;
+  op.degree = ctx->kern_degree;
+  op.gamma = ctx->kern_gamma;
+  op.coef0 = ctx->kern_coef0;
+  if (trans) {
+    op.mr = ctx->n, op.R = ctx->d_kern_x, op.rnrm = ctx->d_kern_nrm, op.sr = ctx->d_kern_scale;
+    op.mc = m, op.C = B.z, op.cnrm = B.znrm;
+  } else {
+    op.mr = m, op.R = B.z, op.rnrm = B.znrm;
+    op.mc = ctx->n, op.C = ctx->d_kern_x, op.cnrm = ctx->d_kern_nrm, op.sc = ctx->d_kern_scale;
+  }
+  return op;
+}
+}  // namespace
+
+int rbl_kernel_cross_splits(int64_t rows, int64_t cols, int d) {
+  if (rows < 1 || cols < 1 || d < 1 || d > RBL_KERNOP_MAX_DIM) return RBL_ERR_INVALID;
+  return kernop_cross_splits(rows, cols, 4 * ((d + 3) / 4));
+}
+
+int rbl_kernel_cross(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int trans, int b, const double* W,
+                     int64_t ldw, double* Y, int64_t ldy) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (!ctx->kernop) return fail(ctx, RBL_ERR_STATE, "rbl_kernel_cross: no kernel matrix");
+  if (trans != 0 && trans != 1) return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_cross: trans must be 0 or 1");
+  if (m < 1 || b < 1 || b > RBL_MAX_BLOCK || m >= ((int64_t)1 << 40) / RBL_MAX_BLOCK)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_cross: m must be >= 1 and b in [1," +
+                                          std::to_string(RBL_MAX_BLOCK) + "]");
+  const int64_t n = ctx->n, wrows = trans ? m : n, yrows = trans ? n : m;
+  if (!Z || !W || !Y || ldz < m || ldw < wrows || ldy < yrows)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_cross: NULL block or a leading dimension below its rows");
+  const int d4 = ctx->kern_d4;
+  std::vector<double> zr, wh((size_t)wrows * b);
+  if (!cross_points(m, ctx->kern_d, d4, Z, ldz, zr))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_cross: Z has a non-finite entry");
+  for (int c = 0; c < b; ++c)
+    for (int64_t i = 0; i < wrows; ++i) {
+      const double v = W[i + c * ldw];
+      if (!std::isfinite(v)) return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_cross: W has a non-finite entry");
+      wh[(size_t)i + (size_t)c * wrows] = v;
+    }
+  HIPC(hipSetDevice(ctx->device));
+  const int S = kernop_cross_splits(yrows, wrows, d4);
+  CrossBufs B;
+  HIPC(B.z.alloc((size_t)m * d4));
+  HIPC(B.znrm.alloc((size_t)m));
+  HIPC(B.w.alloc((size_t)std::max(wrows, yrows) * b));
+  HIPC(B.wr.alloc((size_t)wrows * b));
+  HIPC(B.y.alloc((size_t)yrows * b));
+  if (S > 1) HIPC(B.part.alloc((size_t)S * yrows * b));
+  HIPC(hipMemcpyAsync(B.z, zr.data(), zr.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  kernop_norms(m, d4, B.z, B.znrm, ctx->stream);
+  HIPC(hipMemcpyAsync(B.w, wh.data(), wh.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  colmajor_to_rowmajor(B.w, wrows, b, B.wr, ctx->stream);
+  if (!kernop_cross(cross_op(ctx, B, m, trans), B.wr, b, B.y, B.part, S, ctx->stream))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_cross: shape out of range");
+  HIPC(hipGetLastError());
+  rowmajor_to_colmajor(B.y, yrows, b, B.w, ctx->stream);
+  std::vector<double> yh((size_t)yrows * b);
+  HIPC(hipMemcpyAsync(yh.data(), B.w, yh.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (int c = 0; c < b; ++c) std::copy_n(yh.data() + (size_t)c * yrows, yrows, Y + c * ldy);
+  return RBL_OK;
+}
+
+int rbl_bench_kernel_cross(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int trans, int b, int splits,
+                           int reps, double* ms) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (!ctx->kernop) return fail(ctx, RBL_ERR_STATE, "rbl_bench_kernel_cross: no kernel matrix");
+  if (m < 1 || !Z || ldz < m || (trans != 0 && trans != 1) || b < 1 || b > RBL_MAX_BLOCK || reps < 1 || !ms ||
+      splits < 0 || m >= ((int64_t)1 << 40) / RBL_MAX_BLOCK)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kernel_cross: bad arguments");
+  const int64_t n = ctx->n, wrows = trans ? m : n, yrows = trans ? n : m;
+  const int d4 = ctx->kern_d4;
+  std::vector<double> zr;
+  if (!cross_points(m, ctx->kern_d, d4, Z, ldz, zr))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kernel_cross: Z has a non-finite entry");
+  HIPC(hipSetDevice(ctx->device));
+  const int S = splits ? splits : kernop_cross_splits(yrows, wrows, d4);
+  CrossBufs B;
+  HIPC(B.z.alloc((size_t)m * d4));
+  HIPC(B.znrm.alloc((size_t)m));
+  HIPC(B.wr.alloc((size_t)wrows * b));
+  HIPC(B.y.alloc((size_t)yrows * b));
+  if (S > 1) HIPC(B.part.alloc((size_t)S * yrows * b));
+  HIPC(hipMemcpyAsync(B.z, zr.data(), zr.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  kernop_norms(m, d4, B.z, B.znrm, ctx->stream);
+  randn_block(B.wr, wrows, b, 0, 1, ctx->stream);
+  const KernCross op = cross_op(ctx, B, m, trans);
+  if (!kernop_cross(op, B.wr, b, B.y, B.part, S, ctx->stream))  // warm-up
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kernel_cross: splits out of range for this shape");
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  int st = RBL_OK;
+  if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+  for (int r = 0; r < reps; ++r) kernop_cross(op, B.wr, b, B.y, B.part, S, ctx->stream);
+  if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+  float t = 0.f;
+  if (hipEventElapsedTime(&t, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+  *ms = (double)t / reps;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_kernel_cross: a HIP call failed");
+  return RBL_OK;
+}
+
 int rbl_rect_info(rbl_ctx* ctx, int64_t* nrows, int64_t* ncols, int64_t* nnz) {
   if (!ctx) return RBL_ERR_INVALID;
   if (!ctx->rect) return fail(ctx, RBL_ERR_STATE, "rbl_rect_info: no rectangular matrix");

@@ -14,7 +14,9 @@ square-A drivers takes ``update=(P, S)`` for the implicit operator A + P S P^T (
 diag f(A) by Chebyshev series (``heat_kernel_signature``, ``subgraph_centrality``, ``local_density``,
 ``logdet``); a ``KernelMatrix(X, kind, gamma)`` (``rbl.kernelop``) is the implicit kernel matrix over
 the rows of X as the A of any of these (``RBL_kernel_pca``, ``RBL_spectral_embedding``,
-``kernel_centering_update``); ``Context`` wraps the C-ABI of
+``kernel_centering_update``), and ``kernel_pca_fit`` / ``spectral_embedding_fit`` / ``gp_fit`` keep such a
+fit as a model that serves points outside the training set (``transform``, ``predict``) through the
+cross-kernel product ``Context.kernel_cross``; ``Context`` wraps the C-ABI of
 librbl_hip.so (include/rbl_hip.h).  Importing this package loads the HIP library and fails
 loudly if it has not been built: there is no CPU fallback.
 """
@@ -34,7 +36,8 @@ from .density import (RBL_interval, check_moments, eig_count, interval_degree, i
                       jackson, kpm_count, kpm_density, spectral_density)
 from .lowrank import (RBL_modularity, centering_update, deflation_update,  # noqa: F401
                       modularity_update)
-from .kernelop import (KernelMatrix, RBL_kernel_pca, RBL_spectral_embedding,  # noqa: F401
-                       kernel_centering_update, row_normalize)
+from .kernelop import (GPModel, KernelMatrix, KernelPCAModel, RBL_kernel_pca,  # noqa: F401
+                       RBL_spectral_embedding, SpectralEmbeddingModel, cross_splits, gp_fit,
+                       kernel_centering_update, kernel_pca_fit, row_normalize, spectral_embedding_fit)
 from .funm import (DiagResult, apply_function, cheb_coeffs, cheb_fit, diag_function, diag_series,  # noqa: F401
                    heat_kernel_signature, local_density, logdet, subgraph_centrality, trace_function)

@@ -24,6 +24,8 @@ RBL_ERR_RCCL = -4
 RBL_ERR_STATE = -5
 RBL_ERR_NUMERIC = -6
 
+RBL_MAX_BLOCK = 512          # the largest block width b of any entry point
+
 RBL_OPT_TIMERS = 0
 RBL_OPT_REORTH_ORDER = 1
 RBL_OPT_SPMM_KERNEL = 2
@@ -104,6 +106,9 @@ SIGNATURES = {
     "rbl_kernel_info": (C.c_int, [_p, _pi64, C.POINTER(C.c_int), C.POINTER(C.c_int), _pd, _pd,
                                   C.POINTER(C.c_int), C.POINTER(C.c_int), _pd]),
     "rbl_bench_kernel_pass": (C.c_int, [_p, C.c_int, C.c_int, _pd]),
+    "rbl_kernel_cross": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, _pd, _i64, _pd, _i64]),
+    "rbl_kernel_cross_splits": (C.c_int, [_i64, _i64, C.c_int]),
+    "rbl_bench_kernel_cross": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _pd]),
     "rbl_gen_matrix_hashwindow": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_circuit": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_rmat": (C.c_int, [_p, _i64, C.c_int, _i64, C.c_double, C.c_double, C.c_double,

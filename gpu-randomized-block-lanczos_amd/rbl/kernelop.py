@@ -17,6 +17,11 @@ that takes a matrix takes a KernelMatrix: ``RBL_gpu`` / ``RBL_thick`` (the leadi
 ``kernel_centering_update(ctx)`` is ``rbl.lowrank.centering_update`` for the kernel matrix a context
 holds, from one product with the ones vector; ``RBL_kernel_pca`` and ``RBL_spectral_embedding`` are
 kernel PCA and the normalised spectral embedding on top of these.
+
+A fit is used on points outside the training set through the cross-kernel matrix kappa(Z, X) (m new
+points against the n stored ones), which ``Context.kernel_cross`` multiplies into a block without
+forming it: ``kernel_pca_fit(...).transform(Z)``, ``spectral_embedding_fit(...).transform(Z)`` (the
+Nystrom extension) and ``gp_fit(...).predict(Z, return_var=True)`` / ``.log_marginal_likelihood()``.
 """
 from __future__ import annotations
 
@@ -26,6 +31,18 @@ from . import _lib
 from .rbl_gpu import Context, lanczos
 
 KINDS = {"rbf": _lib.RBL_KERNEL_RBF, "laplace": _lib.RBL_KERNEL_LAPLACE, "poly": _lib.RBL_KERNEL_POLY}
+
+
+def _new_points(what, Z, d):
+    """Z as an m x d fp64 array (a vector is m x 1 for d = 1, one point otherwise), finite, m >= 1."""
+    Z = np.asarray(Z, dtype=np.float64)
+    if Z.ndim == 1:
+        Z = Z.reshape(-1, 1) if d == 1 else Z.reshape(1, -1)
+    if Z.ndim != 2 or Z.shape[0] < 1 or Z.shape[1] != d:
+        raise ValueError(f"{what}: Z must be an m x d array with m >= 1 and d = {d}")
+    if not np.all(np.isfinite(Z)):
+        raise ValueError(f"{what}: Z has a non-finite entry")
+    return Z
 
 
 class KernelMatrix:
@@ -91,6 +108,18 @@ class KernelMatrix:
             d2 += np.subtract.outer(X[:, c], X[:, c]) ** 2
         return np.exp(-self.gamma * (d2 if self.kind == "rbf" else np.sqrt(d2)))
 
+    def cross_array(self, Z) -> np.ndarray:
+        """kappa(Z, X) alone (no scale) as a host fp64 m x n array, distances by direct differences —
+        tests and small sizes only; the device product is ``Context.kernel_cross``."""
+        Z = _new_points("KernelMatrix.cross_array", Z, self.d)
+        X = self.X
+        if self.kind == "poly":
+            return (self.gamma * (Z @ X.T) + self.coef0) ** self.degree
+        d2 = np.zeros((Z.shape[0], self.n))
+        for c in range(self.d):
+            d2 += np.subtract.outer(Z[:, c], X[:, c]) ** 2
+        return np.exp(-self.gamma * (d2 if self.kind == "rbf" else np.sqrt(d2)))
+
     def toarray(self) -> np.ndarray:
         """The operator as a host fp64 n x n array — tests and small n only."""
         K = self.kernel_array()
@@ -123,11 +152,12 @@ def _check_kb(what, n, k, b):
         raise ValueError(f"{what}: k = {k} exceeds n = {n}")
 
 
-def _run(ctx, k, b, max_blocks, omega, seed):
+def _run(ctx, k, b, max_blocks, omega, seed, tol=None):
+    kw = {} if tol is None else {"tol": float(tol)}
     if max_blocks is None:
-        return lanczos(ctx, k, b, omega=omega, seed=seed)
+        return lanczos(ctx, k, b, omega=omega, seed=seed, **kw)
     from .thick import lanczos_thick
-    return lanczos_thick(ctx, k, b, max_blocks=max_blocks, omega=omega, seed=seed)
+    return lanczos_thick(ctx, k, b, max_blocks=max_blocks, omega=omega, seed=seed, **kw)
 
 
 def RBL_kernel_pca(X, k: int, b: int, *, kind: str = "rbf", gamma: float = 1.0, coef0: float = 0.0,
@@ -180,3 +210,265 @@ def RBL_spectral_embedding(X, k: int, b: int, *, kind: str = "rbf", gamma: float
         lam, V, info = _run(ctx, k, b, max_blocks, omega, seed)
     Y = row_normalize(V)
     return (lam, V, Y, info) if return_info else (lam, V, Y)
+
+
+# ---- fits that can be used on points outside the training set: every such use is one product with
+# ---- the cross-kernel matrix kappa(Z, X) (Context.kernel_cross), which is never formed
+
+def cross_splits(rows: int, cols: int, d: int) -> int:
+    """The number of splits of the column range ``Context.kernel_cross`` uses for a rows x cols
+    product in d dimensions (rbl_kernel_cross_splits): a function of the three numbers alone."""
+    s = _lib.lib.rbl_kernel_cross_splits(int(rows), int(cols), int(d))
+    if s < 1:
+        raise ValueError("cross_splits: needs rows >= 1, cols >= 1 and 1 <= d <= "
+                         f"{_lib.RBL_KERNOP_MAX_DIM}")
+    return int(s)
+
+
+# The residual the fits iterate to: a model's eigenpairs are multiplied into every later transform
+# (an eigenvector's error enters lam^-1/2 or lam^-1 times), so they are taken well below the drivers'
+# RESIDUAL_TOL
+FIT_TOL = 1e-10
+
+
+class _KernelFit:
+    """What the three models share: the kernel matrix over the (shifted) training points and the
+    shift new points get before they meet it."""
+
+    def __init__(self, K: KernelMatrix, shift, device: int):
+        self.K = K
+        self.shift = shift
+        self.device = device
+
+    def _points(self, what, Z):
+        return np.asfortranarray(_new_points(what, Z, self.K.d) - self.shift)
+
+
+def _centred_kernel(what, X, kind, gamma, coef0, degree, **kw):
+    """KernelMatrix over X, mean-centred for the two radial kernels (K is unchanged by a shift and
+    the Gram-form cancellation on the device stays small); (K, the shift)."""
+    K = KernelMatrix(X, kind=kind, gamma=gamma, coef0=coef0, degree=degree, **kw)
+    shift = np.zeros(K.d)
+    if kind != "poly":
+        shift = K.X.mean(axis=0)
+        K.X = np.asfortranarray(K.X - shift)
+    return K, shift
+
+
+class KernelPCAModel(_KernelFit):
+    """A fitted kernel PCA (``kernel_pca_fit``).  lam (k, descending, all > 0), V (n x k
+    orthonormal) the eigenpairs of H K H; scores = V sqrt(lam), the training points' coordinates;
+    col_mean = K 1 / n and grand_mean = 1^T K 1 / n^2, the training means the centring of a new
+    point needs; X the training points as the kernel sees them (minus ``shift`` for the radial
+    kernels)."""
+
+    def __init__(self, K, shift, device, lam, V, col_mean, grand_mean, info):
+        super().__init__(K, shift, device)
+        self.lam, self.V, self.scores = lam, V, V * np.sqrt(lam)
+        self.col_mean, self.grand_mean, self.info = col_mean, grand_mean, info
+
+    @property
+    def X(self):
+        return self.K.X
+
+    def transform(self, Z) -> np.ndarray:
+        """The coordinates of the m points Z on the k principal axes:
+        (kappa(Z, X) - r 1^T - 1 (K 1 / n)^T + c) V lam^-1/2 with r = kappa(Z, X) 1 / n the row means
+        and c the grand mean — ONE cross product with the block [V lam^-1/2, 1 / n], whose last
+        column is r.  ``transform`` of the training points reproduces ``scores``."""
+        Zs = self._points("KernelPCAModel.transform", Z)
+        n, k = self.V.shape
+        A = self.V / np.sqrt(self.lam)
+        with Context(self.device) as ctx:
+            ctx.set_matrix(self.K)
+            Y = ctx.kernel_cross(Zs, np.column_stack([A, np.full(n, 1.0 / n)]))
+        return pca_transform_algebra(Y[:, :k], Y[:, k], A, self.col_mean, self.grand_mean)
+
+
+def pca_transform_algebra(KA, r, A, col_mean, grand_mean) -> np.ndarray:
+    """(Kz - r 1^T - 1 m^T + c) A from KA = Kz A and the row means r = Kz 1 / n, with m the training
+    column means and c the grand mean: KA - r (1^T A) - 1 (m^T A) + c (1^T A)."""
+    a = A.sum(axis=0)
+    return KA - np.outer(r, a) - (col_mean @ A)[None, :] + grand_mean * a[None, :]
+
+
+def kernel_pca_fit(X, k: int, b: int, *, kind: str = "rbf", gamma: float = 1.0, coef0: float = 0.0,
+                   degree: int = 3, max_blocks=None, omega=None, seed: int = 0, tol: float = FIT_TOL,
+                   device: int = 0) -> KernelPCAModel:
+    """Kernel PCA of the n points X as ``RBL_kernel_pca`` computes it, kept as a model whose
+    ``transform(Z)`` places new points on the same axes.  ValueError if one of the k leading
+    eigenvalues of H K H is not > 0 (an axis of zero variance has no coordinates).  tol: the
+    residual the eigenpairs are iterated to (FIT_TOL, tighter than the drivers')."""
+    K, shift = _centred_kernel("kernel_pca_fit", X, kind, gamma, coef0, degree)
+    _check_kb("kernel_pca_fit", K.n, k, b)
+    with Context(device) as ctx:
+        ctx.set_matrix(K)
+        P, S = kernel_centering_update(ctx)
+        ctx.set_lowrank(P, S)
+        lam, V, info = _run(ctx, k, b, max_blocks, omega, seed, tol)
+    if not np.all(lam > 0.0):
+        raise ValueError(f"kernel_pca_fit: eigenvalue {int(np.argmin(lam > 0.0))} of H K H is not > 0 (lower k)")
+    return KernelPCAModel(K, shift, device, lam, V, P[:, 1].copy(), float(S[0, 0]), info)
+
+
+def nystrom_algebra(KB, dz) -> np.ndarray:
+    """D_z^-1/2 (kappa(Z, X) D^-1/2 V lam^-1) from KB, the product in brackets, and the new points'
+    degrees dz = kappa(Z, X) 1."""
+    if not np.all(dz > 0.0):
+        raise ValueError("a new point has degree kappa(z, X) 1 <= 0")
+    return KB / np.sqrt(dz)[:, None]
+
+
+class SpectralEmbeddingModel(_KernelFit):
+    """A fitted normalised spectral embedding (``spectral_embedding_fit``): deg = K 1, (lam, V) the k
+    leading eigenpairs of D^-1/2 K D^-1/2, Y the rows of V at unit length."""
+
+    def __init__(self, K, shift, device, deg, lam, V, info):
+        super().__init__(K, shift, device)
+        self.deg, self.lam, self.V, self.Y, self.info = deg, lam, V, row_normalize(V), info
+
+    def transform(self, Z, normalize: bool = True) -> np.ndarray:
+        """The Nystrom extension of the embedding to the m points Z:
+        D_z^-1/2 kappa(Z, X) D^-1/2 V lam^-1 with d_z = kappa(Z, X) 1 — one cross product with the
+        block [V lam^-1, deg^1/2] against the operator's scale deg^-1/2, whose last column is d_z.
+        Rows at unit length unless normalize=False; a training point lands on its own row of V (Y)."""
+        Zs = self._points("SpectralEmbeddingModel.transform", Z)
+        k = self.V.shape[1]
+        with Context(self.device) as ctx:
+            ctx.set_matrix(self.K)
+            Yc = ctx.kernel_cross(Zs, np.column_stack([self.V / self.lam, np.sqrt(self.deg)]))
+        E = nystrom_algebra(Yc[:, :k], Yc[:, k])
+        return row_normalize(E) if normalize else E
+
+
+def spectral_embedding_fit(X, k: int, b: int, *, kind: str = "rbf", gamma: float = 1.0, coef0: float = 0.0,
+                           degree: int = 3, max_blocks=None, omega=None, seed: int = 0, tol: float = FIT_TOL,
+                           device: int = 0) -> SpectralEmbeddingModel:
+    """The embedding of ``RBL_spectral_embedding`` kept as a model whose ``transform(Z)`` embeds new
+    points by the Nystrom extension.  ValueError for a degree <= 0 or one of the k eigenvalues == 0."""
+    K, shift = _centred_kernel("spectral_embedding_fit", X, kind, gamma, coef0, degree)
+    _check_kb("spectral_embedding_fit", K.n, k, b)
+    with Context(device) as ctx:
+        ctx.set_matrix(K)
+        deg = ctx.apply(np.ones((K.n, 1), order="F"))[:, 0]
+        if not np.all(deg > 0.0):
+            raise ValueError("spectral_embedding_fit: a point has degree K 1 <= 0")
+        K.scale = deg ** -0.5
+        ctx.set_kernel_scale(K.scale)
+        lam, V, info = _run(ctx, k, b, max_blocks, omega, seed, tol)
+    if np.any(lam == 0.0):
+        raise ValueError("spectral_embedding_fit: a zero eigenvalue has no Nystrom extension (lower k)")
+    return SpectralEmbeddingModel(K, shift, device, deg, lam, V, info)
+
+
+def _inverse(x):
+    return 1.0 / x
+
+
+class GPModel(_KernelFit):
+    """A fitted Gaussian-process regression (``gp_fit``): alpha = (K + noise I)^-1 y (n x t), the
+    spectrum bounds (lo, hi) and the Chebyshev coefficients of 1 / x on them that every solve uses."""
+
+    def __init__(self, K, shift, device, y, alpha, bounds, coef, tol, vec):
+        super().__init__(K, shift, device)
+        self.y, self.alpha, self.bounds, self.coef, self.tol, self._vec = y, alpha, bounds, coef, tol, vec
+
+    @property
+    def noise(self) -> float:
+        return self.K.nugget
+
+    def _prior_var(self, Zs):
+        if self.K.kind != "poly":
+            return np.ones(Zs.shape[0])
+        return (self.K.gamma * (Zs * Zs).sum(axis=1) + self.K.coef0) ** self.K.degree
+
+    def predict(self, Z, return_var: bool = False):
+        """The predictive mean kappa(Z, X) alpha at the m points Z (m, or m x t for an n x t y), and
+        with return_var the variance of the latent function there,
+        kappa(z, z) - k_z^T (K + noise I)^-1 k_z  (add ``noise`` for that of an observation):
+        C = kappa(X, Z) from the transposed cross product on identity columns (chunks of at most
+        RBL_MAX_BLOCK points), S = (K + noise I)^-1 C by the series of the fit, var = kappa(z, z) -
+        colsum(C o S).  The series is accurate to ``tol`` relative to 1 / lo, so a variance is
+        accurate to about tol kappa(z, z) hi / lo; values below that can come out slightly negative
+        and are returned clipped at 0."""
+        Zs = self._points("GPModel.predict", Z)
+        m = Zs.shape[0]
+        with Context(self.device) as ctx:
+            ctx.set_matrix(self.K)
+            mean = ctx.kernel_cross(Zs, self.alpha)
+            mean = mean[:, 0] if self._vec else mean
+            if not return_var:
+                return mean
+            ctx.set_filter_series(self.bounds[0], self.bounds[1], self.coef)
+            var = self._prior_var(Zs)
+            for c0 in range(0, m, _lib.RBL_MAX_BLOCK):
+                Zc = Zs[c0:c0 + _lib.RBL_MAX_BLOCK]
+                C = ctx.kernel_cross(Zc, np.eye(Zc.shape[0]), trans=True)
+                for j0 in range(0, C.shape[1], _SOLVE_CHUNK):
+                    Cj = C[:, j0:j0 + _SOLVE_CHUNK]
+                    var[c0 + j0:c0 + j0 + Cj.shape[1]] -= (Cj * ctx.apply_filter(Cj)).sum(axis=0)
+        return mean, np.maximum(var, 0.0)
+
+    def log_marginal_likelihood(self, nvec: int = 64, seed: int = 0):
+        """(estimate, stderr) of log p(y | X) = -1/2 y^T alpha - 1/2 log det(K + noise I) - n / 2
+        log 2 pi, summed over the t columns of y.  The log det term is a Hutchinson estimate over
+        nvec Gaussian probes (``rbl.logdet`` on the bounds of the fit); stderr is its standard error
+        carried to the result (t / 2 times the estimator's) — the data-fit term is exact to the
+        solver's tolerance."""
+        from .funm import _trace_on
+        n, t = self.y.shape
+        with Context(self.device) as ctx:
+            ctx.set_matrix(self.K)
+            ld, err = _trace_on(ctx, np.log, self.bounds[0], self.bounds[1], nvec, None, max(self.tol, 1e-12),
+                                seed, None)
+        fit = float(np.sum(self.y * self.alpha))
+        return -0.5 * fit - 0.5 * t * ld - 0.5 * n * t * np.log(2.0 * np.pi), 0.5 * t * err
+
+
+_SOLVE_CHUNK = 64   # columns per rbl_apply_filter call, as rbl.funm.APPLY_CHUNK
+
+
+def gp_fit(X, y, *, kind: str = "rbf", gamma: float = 1.0, noise: float, coef0: float = 0.0, degree: int = 3,
+           tol: float = 1e-10, bounds=None, device: int = 0) -> GPModel:
+    """Gaussian-process regression on the n points X with targets y (n, or n x t for t outputs) and
+    observation noise variance ``noise`` > 0: alpha = (K + noise I)^-1 y by ``apply_function`` with
+    f = 1 / x, K never formed; ``predict`` and ``log_marginal_likelihood`` on the model.
+
+    The solver is ``apply_function``'s Chebyshev series of 1 / x on [lo, hi] and has its limits: the
+    degree grows like sqrt(hi / lo) log(1 / tol), so it suits K + noise I of moderate condition number
+    (noise not many orders below the largest eigenvalue, at most n for the radial kernels); there is
+    no Krylov solver here.  bounds=(lo, hi) must enclose the spectrum of K + noise I with lo > 0.
+    None: for the positive semi-definite kernels (rbf, laplace, poly with coef0 >= 0) lo = 0.99
+    noise; hi = 1.01 max((K + noise I) 1) for the two radial kernels (entries >= 0: a row sum bounds
+    the spectrum), else the estimate of ``estimate_spectrum``."""
+    if isinstance(noise, bool) or not np.isscalar(noise) or not np.isfinite(noise) or not noise > 0:
+        raise ValueError("gp_fit: noise must be a finite number > 0")
+    if not np.isscalar(tol) or not 0 < tol < 1:
+        raise ValueError("gp_fit: tol must be in (0, 1)")
+    K, shift = _centred_kernel("gp_fit", X, kind, gamma, coef0, degree, nugget=noise)
+    y = np.asarray(y, dtype=np.float64)
+    vec = y.ndim == 1
+    if vec:
+        y = y[:, None]
+    if y.ndim != 2 or y.shape[0] != K.n or y.shape[1] < 1:
+        raise ValueError(f"gp_fit: y must have n = {K.n} rows")
+    if not np.all(np.isfinite(y)):
+        raise ValueError("gp_fit: y has a non-finite entry")
+    from .density import _bounds
+    from .funm import apply_function, cheb_fit
+    with Context(device) as ctx:
+        ctx.set_matrix(K)
+        if bounds is not None:
+            (lo, hi), _ = _bounds(ctx, bounds, 0)
+        else:
+            if kind != "poly":
+                lo, hi = 0.0, 1.01 * float(ctx.apply(np.ones((K.n, 1), order="F")).max())
+            else:
+                (lo, hi), _ = _bounds(ctx, None, 0)
+            if kind != "poly" or coef0 >= 0:
+                lo = 0.99 * float(noise)
+        if not lo > 0:
+            raise ValueError(f"gp_fit: the lower spectrum bound {lo} is not > 0 (pass bounds=(lo, hi))")
+    coef = cheb_fit(_inverse, lo, hi, tol)       # the series apply_function fits; predict reuses it
+    alpha = apply_function(K, _inverse, y, tol=tol, bounds=(lo, hi), device=device)
+    return GPModel(K, shift, device, y, alpha, (lo, hi), coef, float(tol), vec)

@@ -295,6 +295,43 @@ class Context:
         self._check(lib.rbl_bench_kernel_pass(self._h, int(b), int(reps), dptr(ms)), "rbl_bench_kernel_pass")
         return float(ms[0])
 
+    def _cross_points(self, what, Z):
+        from .kernelop import _new_points
+        info = self.kernel_info()
+        return np.asfortranarray(_new_points(what, Z, info["d"])), info["n"]
+
+    def kernel_cross(self, Z, W, trans: bool = False) -> np.ndarray:
+        """The cross-kernel product of the kernel matrix held (points X, scale s) with the m new
+        points Z (m x d) (rbl_kernel_cross): Y (m x b) = kappa(Z, X) diag(s) W for W n x b, or with
+        trans Y (n x b) = diag(s) kappa(X, Z) W for W m x b.  kappa(Z, X) is never formed; the
+        nugget does not enter and no pair is treated as "the same point".  Two calls give the same
+        bits."""
+        Z, n = self._cross_points("kernel_cross", Z)
+        m = Z.shape[0]
+        rin, rout = (m, n) if trans else (n, m)
+        W = np.asarray(W, dtype=np.float64)
+        if W.ndim == 1:
+            W = W.reshape(-1, 1)
+        if W.ndim != 2 or W.shape[0] != rin or W.shape[1] < 1:
+            raise ValueError(f"kernel_cross: W must have {rin} rows and at least one column")
+        if not np.all(np.isfinite(W)):
+            raise ValueError("kernel_cross: W has a non-finite entry")
+        W = np.asfortranarray(W)
+        Y = np.zeros((rout, W.shape[1]), order="F")
+        self._check(lib.rbl_kernel_cross(self._h, m, dptr(Z), m, int(bool(trans)), W.shape[1], dptr(W), rin,
+                                         dptr(Y), rout), "rbl_kernel_cross")
+        return Y
+
+    def bench_kernel_cross(self, Z, b: int, trans: bool = False, splits: int = 0, reps: int = 5) -> float:
+        """Milliseconds per cross-kernel product of the matrix held with the points Z and a
+        device-resident block of b columns (rbl_bench_kernel_cross); splits = 0: the library's rule."""
+        Z, _ = self._cross_points("bench_kernel_cross", Z)
+        ms = np.zeros(1)
+        self._check(lib.rbl_bench_kernel_cross(self._h, Z.shape[0], dptr(Z), Z.shape[0], int(bool(trans)),
+                                               int(b), int(splits), int(reps), dptr(ms)),
+                    "rbl_bench_kernel_cross")
+        return float(ms[0])
+
     # -- implicit symmetric low-rank update: the operator A + P S P^T ------------------------
     def set_lowrank(self, P, S) -> None:
         """The operator becomes A + P S P^T (rbl_set_lowrank): P n x r, S r x r symmetric,

@@ -324,6 +324,36 @@ int rbl_kernel_info(rbl_ctx* ctx, int64_t* n, int* d, int* kind, double* gamma, 
 /* Milliseconds per application of the kernel matrix held to a device-resident N(0,1) block of b
  * columns: one warm-up pass, then `reps` passes between two hipEvents.  RBL_ERR_STATE without one. */
 int rbl_bench_kernel_pass(rbl_ctx* ctx, int b, int reps, double* ms);
+/* Cross-kernel product of the kernel matrix held (points X, n x d; scale s) with m new points Z
+ * (m x d, column-major, ldz >= m) — what every out-of-sample use of a kernel fit needs (kernel PCA's
+ * transform, the Nystrom extension, a Gaussian process's mean and variance):
+ *   trans = 0:  Y (m x b) = kappa(Z, X) diag(s) W,   W n x b  (ldw >= n, ldy >= m)
+ *   trans = 1:  Y (n x b) = diag(s) kappa(X, Z) W,   W m x b  (ldw >= m, ldy >= n)
+ * host column-major blocks like rbl_apply.  kappa(Z, X) is evaluated tile by tile on fp64 MFMA and
+ * never stored; any 1 <= b <= RBL_MAX_BLOCK runs on MFMA (column chunks of 32 and 16, a narrower
+ * last chunk zero-padded to 16).  The nugget never enters and there is no diagonal rule: where a row
+ * of Z coincides with a row of X the entry is kappa of the Gram-form distance, within rounding of
+ * kappa(0) and not exactly it.  The column range is split over rbl_kernel_cross_splits(rows of Y,
+ * rows of W, d) workgroup columns, whose partials are added in ascending order by one thread per
+ * output: no atomics, two calls give the same bits, and the bits do not depend on the device's CU
+ * count.  Runs on the context's stream; extra device memory for the call only: the points of Z, the
+ * two blocks and splits x rows x b doubles of partials.
+ * RBL_ERR_STATE without a kernel matrix; RBL_ERR_INVALID for m < 1, b outside [1, RBL_MAX_BLOCK],
+ * trans not 0 or 1, a NULL pointer, a leading dimension below its block's rows, or a non-finite
+ * entry of Z or W — the context unchanged (a following rbl_apply gives the bits of one before). */
+int rbl_kernel_cross(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int trans, int b,
+                     const double* W, int64_t ldw, double* Y, int64_t ldy);
+/* The number of splits S of the column range rbl_kernel_cross uses for a rows x cols product in d
+ * dimensions — a function of the three numbers alone (no context, no device): the fewest splits with
+ * ceil(rows / 64) S >= 512 workgroups, at most 64, each split at least 4 stages of 64 (d <= 16), 32
+ * (d <= 64) or 16 column points; 1 when rows >= 32705.  RBL_ERR_INVALID for a bad argument. */
+int rbl_kernel_cross_splits(int64_t rows, int64_t cols, int d);
+/* Milliseconds per cross-kernel product of the matrix held with the m points Z against a
+ * device-resident N(0,1) block of b columns (the device part of rbl_kernel_cross alone): one warm-up,
+ * then `reps` products between two hipEvents.  splits = 0: the rule above; otherwise that many
+ * (RBL_ERR_INVALID beyond 64 or the stages of the column range). */
+int rbl_bench_kernel_cross(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int trans, int b,
+                           int splits, int reps, double* ms);
 int rbl_gen_matrix_hashwindow(rbl_ctx* ctx, int64_t n, int64_t halfwidth, double density,
                               uint64_t seed, int nplant, const double* plant);
 /* Device-side generator of the seeded symmetric R-MAT matrix (BASELINE

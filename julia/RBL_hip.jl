@@ -325,6 +325,43 @@ function RBL_gpu_kernel(X::Matrix{Float64}, k::Int64, b::Int64; kind::Symbol = :
     return RBL_hip(K, k, b; timer = timer, basis_bits = 64, seed = seed, update = update)
 end
 
+# The cross-kernel product of the kernel matrix a context holds (points X, n x d; scale s) with the
+# m new points Z (m x d): trans = false  Y (m x b) = kappa(Z, X) diag(s) W, W n x b;  trans = true
+# Y (n x b) = diag(s) kappa(X, Z) W, W m x b (rbl_kernel_cross).  kappa(Z, X) is never formed, the
+# nugget does not enter, and no pair of points is treated as the same point.
+function kernel_cross(ctx::Ptr{Cvoid}, Z::Matrix{Float64}, W::Matrix{Float64}; trans::Bool = false)
+    nref = zeros(Int64, 1)
+    rbl_check(ctx, ccall((:rbl_kernel_info, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Ptr{Int64}, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint},
+                          Ptr{Cint}, Ptr{Float64}),
+                         ctx, nref, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL), "rbl_kernel_info")
+    m = size(Z, 1)
+    rin, rout = trans ? (m, nref[1]) : (nref[1], m)
+    size(W, 1) == rin || throw(ArgumentError("kernel_cross: W must have $rin rows"))
+    Y = zeros(Float64, rout, size(W, 2))
+    rbl_check(ctx, ccall((:rbl_kernel_cross, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Cint, Cint, Ptr{Float64}, Int64, Ptr{Float64},
+                          Int64),
+                         ctx, m, Z, m, Cint(trans), Cint(size(W, 2)), W, rin, Y, rout), "rbl_kernel_cross")
+    return Y
+end
+
+# Out-of-sample use of a kernel fit on the n training points X: kappa(Z, X) diag(scale) W for the
+# m new points Z — a Gaussian process's predictive mean with W = alpha = (K + tau I)^-1 y, kernel
+# PCA's transform with W = [V lam^-1/2 1/n], the Nystrom extension with scale = deg .^ -0.5 and
+# W = [V lam^-1 deg .^ 0.5].  One context: set_matrix!(::KernelPoints), kernel_cross, free.
+function RBL_gpu_kernel_predict(X::Matrix{Float64}, W::Matrix{Float64}, Z::Matrix{Float64};
+                                kind::Symbol = :rbf, gamma::Float64 = 1.0, coef0::Float64 = 0.0,
+                                degree::Int = 3, scale = nothing, device::Int = 0)
+    ctx = rbl_context(device)
+    try
+        set_matrix!(ctx, KernelPoints(X, kind, gamma, coef0, degree, scale, 0.0))
+        return kernel_cross(ctx, Z, W)
+    finally
+        ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
+    end
+end
+
 # Drop-in for images.jl:29-33 on a sparse rectangular B: `D, V = RBL_gpu(transpose(B)*B, k, b)`,
 # `D = sqrt.(D)`, `U = (B*V) ./ transpose(D)` — without forming B^T B (rbl_set_matrix_normal).
 # Returns U (m x k), the singular values D (descending) and V (n x k).  The fp64 basis only.

@@ -11,7 +11,9 @@ wall time of the same Context.apply (host block in, host block out) for both ope
 b = --dense-b, `--rounds` rounds of `--reps` calls, median per call — the host transfers are in
 both numbers.
 
-Writes one JSON document (default profiles/kernelop_bench.json)."""
+Writes one JSON document (default profiles/kernelop_bench.json).
+
+--cross times the cross-kernel product kappa(Z, X) W (kernelop_cross.hip) instead: see cross()."""
 import argparse
 import json
 import os
@@ -53,8 +55,60 @@ def materialise(X, gamma, rows=2048):
     return K
 
 
+def cross(args):
+    """--cross: rbl_bench_kernel_cross (hipEvents around `--reps` products after one warm-up, a
+    device-resident N(0,1) block) for each (m, n, d, b) of --cross-shapes, kappa(Z, X) W with Z m
+    fresh points of the same blobs: the library's split of the column range, the same product with
+    the split forced to S = 1, and — for a square shape — rbl_bench_kernel_pass of the symmetric
+    operator over X at the same n, d, b, the yardstick of the pair-evaluation rate.  The variants of
+    one shape alternate within a round (one process, one device); medians over `--rounds` rounds."""
+    if len(args.cross_shapes) % 4:
+        raise SystemExit("--cross-shapes takes m n d b quadruples")
+    shapes = [tuple(args.cross_shapes[i:i + 4]) for i in range(0, len(args.cross_shapes), 4)]
+
+    import rbl
+
+    doc = {"kernel": "rbf", "gamma": args.gamma, "reps": args.reps, "rounds": args.rounds, "cross": []}
+    for m, n, d, b in shapes:
+        X, Z = points(n, d), points(m, d, seed=1)
+        S = rbl.cross_splits(m, n, d)
+        with rbl.Context(0) as ctx:
+            ctx.set_matrix_kernel(X, "rbf", args.gamma)
+            runs = {"split": lambda: ctx.bench_kernel_cross(Z, b, splits=0, reps=args.reps),
+                    "unsplit": lambda: ctx.bench_kernel_cross(Z, b, splits=1, reps=args.reps)}
+            if m == n:
+                runs["symmetric"] = lambda: ctx.bench_kernel_pass(b, args.reps)
+            for fn in runs.values():
+                fn()                                              # warm every variant once
+            times = {name: [] for name in runs}
+            for _ in range(args.rounds):
+                for name, fn in runs.items():
+                    times[name].append(fn())
+        row = {"m": m, "n": n, "d": d, "b": b, "splits": S,
+               "workgroups": -(-m // 64) * S, "workgroups_unsplit": -(-m // 64)}
+        for name, t in times.items():
+            row[f"ms_{name}"] = statistics.median(t)
+            row[f"ms_{name}_rounds"] = t
+        row["pairs_per_s"] = m * n / (row["ms_split"] * 1e-3)
+        row["unsplit_over_split"] = row["ms_unsplit"] / row["ms_split"]
+        if m == n:
+            row["cross_over_symmetric"] = row["ms_split"] / row["ms_symmetric"]
+        doc["cross"].append(row)
+        print(json.dumps(row), flush=True)
+    out = args.out if args.out else os.path.join(ROOT, "profiles", "kernelop_cross_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cross", action="store_true",
+                    help="time the cross-kernel product instead (profiles/kernelop_cross_bench.json)")
+    ap.add_argument("--cross-shapes", type=int, nargs="+",
+                    default=[256, 131072, 16, 1, 256, 131072, 16, 32, 32768, 32768, 16, 32],
+                    help="m n d b quadruples of --cross")
     ap.add_argument("--shapes", type=int, nargs="+",
                     default=[32768, 16, 32, 32768, 128, 32, 32768, 16, 16, 131072, 16, 32],
                     help="n d b triples")
@@ -64,8 +118,13 @@ def main():
     ap.add_argument("--dense-n", type=int, default=32768)
     ap.add_argument("--dense-d", type=int, default=16)
     ap.add_argument("--dense-b", type=int, default=32)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kernelop_bench.json"))
+    ap.add_argument("--out", default=None,
+                    help="default profiles/kernelop_bench.json, profiles/kernelop_cross_bench.json with --cross")
     args = ap.parse_args()
+    if args.cross:
+        return cross(args)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "kernelop_bench.json")
     if len(args.shapes) % 3:
         ap.error("--shapes takes n d b triples")
     shapes = [tuple(args.shapes[i:i + 3]) for i in range(0, len(args.shapes), 3)]
