@@ -372,6 +372,51 @@ void lr_small(int r, int rp, int b, const double* S, const double* w, double* c,
 void lr_update(int64_t rows, int b, int rp, const double* P, const double* c, double* U,
                hipStream_t s);
 
+// --- cg.hip: the row passes of the batched preconditioned CG solver (rbl_solve) -------------------
+// X, R, P, W, B: n x b row-major blocks, 1 <= b <= RBL_MAX_BLOCK; part holds cg_grid(nrows, b) x 2 b
+// doubles (the workgroup partials of a pass, added into `dots` by reduce_slab).  Fixed summation
+// orders, no atomics; 16-byte accesses when b is even and every block is 16-byte aligned.
+// The per-column scalars, b entries each, on the device.  status: kCgActive while the column
+// iterates, then kCgConverged or kCgNotPosDef (a frozen column: its x, r, p are not stored again).
+// hist (null: none): (alpha_j, beta_j) of iteration j at hist[(2 j + {0, 1}) * b + column].
+constexpr int kCgActive = -1, kCgConverged = 0, kCgNotPosDef = 2;
+struct CgScalars {
+  double* rho = nullptr;
+  double* alpha = nullptr;
+  double* beta = nullptr;
+  double* bb = nullptr;   // |b|^2
+  double* rr = nullptr;   // |r|^2 of the recurrence
+  int* iters = nullptr;
+  int* status = nullptr;
+  int* nactive = nullptr;  // one int: the columns still active after the last cg_beta
+  double* hist = nullptr;
+};
+int cg_grid(int64_t nrows, int b);
+//   cg_resid:  R = B - (W + sigma X) (X null: R = B; W, X not read), dots = [|b|^2 (b), |r|^2 (b)];
+//   cg_dot:    dots[c] = p_c^T (w_c + sigma p_c);
+//   cg_alpha:  alpha = rho / pap (one workgroup); 0 for a frozen column; pap <= 0 or not finite
+//              freezes the column as kCgNotPosDef;
+//   cg_update: x += alpha p, r -= alpha (w + sigma p) on the active columns, dots[c] = |r_c|^2;
+//   cg_small:  c = diag(dv) w (w, c: rp x b row-major; dv: rp entries);
+//   cg_beta:   rho' = |r|^2 + w^T c (rp > 0; w = V^T r, c = dv o w), beta = rho' / rho, the iteration
+//              counted, (alpha, beta) appended to hist at `iter`, the column frozen as kCgConverged
+//              once |r|^2 <= tol2 |b|^2, *nactive counted (one workgroup).  init: dots is cg_resid's,
+//              the scalars are set up (iters = 0, beta = 0) and nothing is appended;
+//   cg_dir:    p = r + V c + beta p on the active columns (rp = 0: p = r + beta p; else V: nrows x rp
+//              row-major, rp = lr_padded_width(r), as lr_update's P).
+void cg_resid(int64_t nrows, int b, const double* B, const double* W, const double* X, double sigma,
+              double* R, double* part, double* dots, hipStream_t s);
+void cg_dot(int64_t nrows, int b, const double* P, const double* W, double sigma, double* part,
+            double* dots, hipStream_t s);
+void cg_alpha(int b, const double* pap, const CgScalars& sc, hipStream_t s);
+void cg_update(int64_t nrows, int b, double* X, double* R, const double* P, const double* W, double sigma,
+               const CgScalars& sc, double* part, double* dots, hipStream_t s);
+void cg_small(int rp, int b, const double* dv, const double* w, double* c, hipStream_t s);
+void cg_beta(int b, int rp, bool init, int iter, const double* dots, const double* w, const double* c,
+             double tol2, const CgScalars& sc, hipStream_t s);
+void cg_dir(int64_t nrows, int b, int rp, const double* R, double* P, const double* V, const double* c,
+            const CgScalars& sc, hipStream_t s);
+
 // --- kernelop.hip: the implicit kernel matrix (rbl_set_matrix_kernel) ---------------------------
 // Op = diag(scale) K diag(scale) + nugget I, K_ij = kappa(x_i, x_j) over the n points X (device,
 // row-major n x d4, d4 = 4 ceil(d / 4) <= kKernMaxDim, the columns past d zero; nrm[i] = |x_i|^2

@@ -167,7 +167,16 @@ struct LowrankBufs {
   DevBuf<double> d_lr_part;
 };
 
-struct MatrixBufs : PanelBufs, SegTableBufs, TierBufs, RectShiftBufs, LowrankBufs {
+// spectral preconditioner of rbl_solve, M^-1 = I + V diag(dv) V^T (rbl_set_precond_lowrank;
+// free_precond).  d_pc_V: n_local x pc_rp row-major, the columns past pc_r zero (pc_rp =
+// lr_padded_width(pc_r)); d_pc_dv: pc_rp entries, zero past pc_r.  Its own buffers: the operator's
+// low-rank update (LowrankBufs) may be set at the same time.
+struct PrecondBufs {
+  DevBuf<double> d_pc_V;
+  DevBuf<double> d_pc_dv;
+};
+
+struct MatrixBufs : PanelBufs, SegTableBufs, TierBufs, RectShiftBufs, LowrankBufs, PrecondBufs {
   DevBuf<int64_t> d_rowptr;
   DevBuf<int32_t> d_col;
   DevBuf<double> d_val;
@@ -309,6 +318,8 @@ struct rbl_ctx : rbl::api::MatrixBufs, rbl::api::RunBufs, rbl::api::CtxBufs {
   // by apply_A after the SpMM
   int lr_r = 0, lr_rp = 0;
   int lr_cols = 0;
+  // spectral preconditioner of rbl_solve (rbl_set_precond_lowrank): rank and padded width; 0: none
+  int pc_r = 0, pc_rp = 0;
   int64_t ntiles = 0, tiles_per_wg = 0;
   bool window_ok16 = false, window_ok32 = false;
   bool band_ok16 = false, band_ok32 = false;
@@ -2505,12 +2516,19 @@ void free_lowrank(rbl_ctx* ctx) {
   ctx->lr_r = ctx->lr_rp = 0;
 }
 
+// the preconditioner of rbl_solve
+void free_precond(rbl_ctx* ctx) {
+  static_cast<PrecondBufs&>(*ctx) = PrecondBufs{};
+  ctx->pc_r = ctx->pc_rp = 0;
+}
+
 void free_matrix(rbl_ctx* ctx) {
   // the parts that are also released alone reset their own scalars; then every matrix buffer
   free_panels(ctx);
   free_tiers(ctx);
   free_rect_shift(ctx);
   free_lowrank(ctx);
+  free_precond(ctx);
   static_cast<MatrixBufs&>(*ctx) = MatrixBufs{};
   ctx->bt_ng = 0;
   ctx->seg_ntasks = ctx->seg_nlong = 0;
@@ -4797,6 +4815,275 @@ int rbl_bench_lowrank_pass(rbl_ctx* ctx, int64_t rows, int b, int r, int reps, d
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   if (st != RBL_OK) return fail(ctx, st, "rbl_bench_lowrank_pass: a HIP call failed");
+  return RBL_OK;
+}
+
+// ---- preconditioned conjugate gradients: (Op + shift I) X = B -----------------------------------
+int rbl_set_precond_lowrank(rbl_ctx* ctx, int r, const double* V, const double* dv) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (ctx->nranks > 1)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_precond_lowrank: one rank only (nranks > 1 is not supported)");
+  if (!has_matrix(ctx)) return fail(ctx, RBL_ERR_STATE, "rbl_set_precond_lowrank: no matrix");
+  if (ctx->rect)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_set_precond_lowrank: not with a rectangular B (rbl_set_matrix_normal)");
+  if (r < 1 || r > 32) return fail(ctx, RBL_ERR_INVALID, "rbl_set_precond_lowrank: r must be in [1, 32]");
+  if (!V || !dv) return fail(ctx, RBL_ERR_INVALID, "rbl_set_precond_lowrank: V or dv is NULL");
+  const int64_t n = ctx->nloc;
+  for (int64_t i = 0; i < n * r; ++i)
+    if (!std::isfinite(V[i])) return fail(ctx, RBL_ERR_INVALID, "rbl_set_precond_lowrank: V has a non-finite entry");
+  for (int i = 0; i < r; ++i)
+    if (!std::isfinite(dv[i]) || !(dv[i] > -1.0))
+      return fail(ctx, RBL_ERR_INVALID, "rbl_set_precond_lowrank: dv[" + std::to_string(i) +
+                                            "] must be finite and > -1 (I + V diag(dv) V^T positive definite)");
+  HIPC(hipSetDevice(ctx->device));
+  // V column-major n x r -> row-major n x rp, the padding columns zero
+  const int rp = lr_padded_width(r);
+  std::vector<double> Vr((size_t)std::max<int64_t>(n, 1) * rp, 0.0), dvp((size_t)rp, 0.0);
+  for (int j = 0; j < r; ++j)
+    for (int64_t i = 0; i < n; ++i) Vr[(size_t)i * rp + j] = V[i + (size_t)j * n];
+  std::copy(dv, dv + r, dvp.begin());
+  HIPC(hipStreamSynchronize(ctx->stream));
+  PrecondBufs nb;  // the context keeps its preconditioner unless every step below succeeds
+  HIPC(nb.d_pc_V.alloc(Vr.size()));
+  HIPC(nb.d_pc_dv.alloc(dvp.size()));
+  HIPC(hipMemcpy(nb.d_pc_V, Vr.data(), Vr.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(nb.d_pc_dv, dvp.data(), dvp.size() * sizeof(double), hipMemcpyHostToDevice));
+  static_cast<PrecondBufs&>(*ctx) = std::move(nb);
+  ctx->pc_r = r;
+  ctx->pc_rp = rp;
+  return RBL_OK;
+}
+
+int rbl_clear_precond(rbl_ctx* ctx) {
+  if (!ctx) return RBL_ERR_INVALID;
+  HIPC(hipSetDevice(ctx->device));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  free_precond(ctx);
+  return RBL_OK;
+}
+
+namespace {
+
+// Every device buffer of one rbl_solve / rbl_bench_cg_pass call: released on every return path.
+struct CgBufs {
+  DevBuf<double> B, X, R, P, W;  // n x b row-major blocks, (n_local + kRowPad) x b, zeroed
+  DevBuf<double> part;           // workgroup partials of a pass (cg_grid x 2 b)
+  DevBuf<double> dots;           // their sums (2 b)
+  DevBuf<double> sc;             // rho, alpha, beta, |b|^2, |r|^2 (b each)
+  DevBuf<int> isc;               // iters (b), status (b), nactive (1)
+  DevBuf<double> hist;           // (alpha, beta) per iteration (2 max_iter b), or empty
+  DevBuf<double> wc;             // preconditioner: w = V^T r and c = dv o w (rp x b each)
+  DevBuf<double> lrpart;         //   and the workgroup partials of w
+  CgScalars scalars(int b) const {
+    CgScalars s;
+    s.rho = sc;
+    s.alpha = sc + b;
+    s.beta = sc + 2 * b;
+    s.bb = sc + 3 * b;
+    s.rr = sc + 4 * b;
+    s.iters = isc;
+    s.status = isc + b;
+    s.nactive = isc + 2 * b;
+    s.hist = hist;
+    return s;
+  }
+};
+
+int cg_alloc(rbl_ctx* ctx, CgBufs& g, int64_t rows, int b, int rp, size_t hist_len) {
+  const size_t padded = (size_t)(std::max<int64_t>(rows, 1) + kRowPad) * b;
+  for (DevBuf<double>* p : {&g.B, &g.X, &g.R, &g.P, &g.W}) {
+    HIPC(p->alloc(padded));
+    HIPC(hipMemsetAsync(*p, 0, padded * sizeof(double), ctx->stream));
+  }
+  HIPC(g.part.alloc((size_t)cg_grid(rows, b) * 2 * b));
+  HIPC(g.dots.alloc((size_t)2 * b));
+  HIPC(g.sc.alloc((size_t)5 * b));
+  HIPC(hipMemsetAsync(g.sc, 0, (size_t)5 * b * sizeof(double), ctx->stream));
+  HIPC(g.isc.alloc((size_t)2 * b + 1));
+  HIPC(hipMemsetAsync(g.isc, 0, ((size_t)2 * b + 1) * sizeof(int), ctx->stream));
+  if (hist_len) {
+    HIPC(g.hist.alloc(hist_len));
+    HIPC(hipMemsetAsync(g.hist, 0, hist_len * sizeof(double), ctx->stream));
+  }
+  if (rp > 0) {
+    HIPC(g.wc.alloc((size_t)2 * rp * b));
+    HIPC(hipMemsetAsync(g.wc, 0, (size_t)2 * rp * b * sizeof(double), ctx->stream));
+    HIPC(g.lrpart.alloc((size_t)lr_project_grid(rows, b, rp) * rp * b));
+  }
+  return RBL_OK;
+}
+
+}  // namespace
+
+int rbl_solve(rbl_ctx* ctx, int b, const double* B, double* X, double shift, double tol, int max_iter,
+              int check_every, int use_x0, int* iters, int* status, double* resid, double* coef) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (b < 1 || b > RBL_MAX_BLOCK)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_solve: b must be in [1," + std::to_string(RBL_MAX_BLOCK) + "]");
+  if (!B || !X || !iters || !status || !resid)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_solve: B, X, iters, status or resid is NULL");
+  if (!std::isfinite(shift)) return fail(ctx, RBL_ERR_INVALID, "rbl_solve: shift must be finite");
+  if (!std::isfinite(tol) || !(tol > 0.0) || !(tol < 1.0))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_solve: tol must be in (0, 1)");
+  if (max_iter < 1 || max_iter > 65535)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_solve: max_iter must be in [1, 65535]");
+  if (coef && max_iter > 4096)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_solve: with a coefficient history max_iter must be <= 4096");
+  if (check_every < 1) return fail(ctx, RBL_ERR_INVALID, "rbl_solve: check_every must be >= 1");
+  if (ctx->nranks > 1)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_solve: one rank only (nranks > 1 is not supported)");
+  if (!has_matrix(ctx)) return fail(ctx, RBL_ERR_STATE, "rbl_solve: no matrix");
+  if (ctx->rect)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_solve: not with a rectangular B (rbl_set_matrix_normal)");
+  if (ctx->d_basis32)
+    return fail(ctx, RBL_ERR_STATE, "rbl_solve: the fp64 basis only (the current run has basis_bits = 32)");
+  HIPC(hipSetDevice(ctx->device));
+  const int64_t n = ctx->nloc;
+  const int rp = ctx->pc_rp;
+  const size_t hist_len = coef ? (size_t)2 * max_iter * b : 0;
+  CgBufs g;
+  CHK(cg_alloc(ctx, g, n, b, rp, hist_len));
+  const CgScalars sc = g.scalars(b);
+  double *w = g.wc, *c = rp > 0 ? g.wc + (size_t)rp * b : nullptr;
+  hipStream_t st = ctx->stream;
+  // column-major host blocks pass through W, which the first product overwrites
+  HIPC(hipMemcpyAsync(g.W, B, n * b * sizeof(double), hipMemcpyHostToDevice, st));
+  colmajor_to_rowmajor(g.W, n, b, g.B, st);
+  if (use_x0) {
+    HIPC(hipMemcpyAsync(g.W, X, n * b * sizeof(double), hipMemcpyHostToDevice, st));
+    colmajor_to_rowmajor(g.W, n, b, g.X, st);
+  }
+  HIPC(hipGetLastError());
+  auto product = [&](const double* in) -> int {
+    StageScope t(ctx, RBL_STAGE_AQ);
+    const int s = apply_A(ctx, in, 0, b, g.W, nullptr, nullptr, nullptr);
+    return s < 0 ? s : RBL_OK;
+  };
+  // z = M^-1 r through the small quantities: w = V^T r, c = dv o w
+  auto precond = [&] {
+    if (rp == 0) return;
+    lr_project(n, b, rp, ctx->d_pc_V, g.R, g.lrpart, w, st);
+    cg_small(rp, b, ctx->d_pc_dv, w, c, st);
+  };
+  int nactive = 0;
+  auto read_active = [&]() -> int {
+    HIPC(hipMemcpyAsync(&nactive, sc.nactive, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    harvest_timers(ctx);
+    return RBL_OK;
+  };
+  const double tol2 = tol * tol;
+  // with stage timers on, every iteration takes four events from the context's pool, and only a
+  // harvest after a synchronisation returns them: the host then looks at the active count at least
+  // every kCgTimedCheck iterations whatever check_every is (the result does not depend on it)
+  constexpr int kCgTimedCheck = 64;
+  const int every = ctx->timers ? std::min(check_every, kCgTimedCheck) : check_every;
+  if (use_x0) CHK(product(g.X));
+  {
+    StageScope t(ctx, RBL_STAGE_3TERM);
+    cg_resid(n, b, g.B, g.W, use_x0 ? g.X.p : nullptr, shift, g.R, g.part, g.dots, st);
+    precond();
+    cg_beta(b, rp, true, 0, g.dots, w, c, tol2, sc, st);
+    cg_dir(n, b, rp, g.R, g.P, ctx->d_pc_V, c, sc, st);  // beta = 0, P zeroed: p = z
+  }
+  HIPC(hipGetLastError());
+  CHK(read_active());
+  for (int j = 0; j < max_iter && nactive > 0; ++j) {
+    CHK(product(g.P));
+    {
+      StageScope t(ctx, RBL_STAGE_3TERM);
+      cg_dot(n, b, g.P, g.W, shift, g.part, g.dots, st);
+      cg_alpha(b, g.dots, sc, st);
+      cg_update(n, b, g.X, g.R, g.P, g.W, shift, sc, g.part, g.dots, st);
+      precond();
+      cg_beta(b, rp, false, j, g.dots, w, c, tol2, sc, st);
+      cg_dir(n, b, rp, g.R, g.P, ctx->d_pc_V, c, sc, st);
+    }
+    HIPC(hipGetLastError());
+    if ((j + 1) % every == 0 && j + 1 < max_iter) CHK(read_active());
+  }
+  // the true residual b - (Op + shift I) x from the device-resident B (into P, no longer needed)
+  CHK(product(g.X));
+  {
+    StageScope t(ctx, RBL_STAGE_3TERM);
+    cg_resid(n, b, g.B, g.W, g.X, shift, g.P, g.part, g.dots, st);
+  }
+  HIPC(hipGetLastError());
+  std::vector<double> dots((size_t)2 * b), hist(hist_len);
+  std::vector<int> isc((size_t)2 * b + 1);
+  rowmajor_to_colmajor(g.X, n, b, g.W, st);
+  HIPC(hipMemcpyAsync(X, g.W, n * b * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(dots.data(), g.dots, dots.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(isc.data(), g.isc, isc.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (hist_len) HIPC(hipMemcpyAsync(hist.data(), g.hist, hist_len * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  harvest_timers(ctx);
+  for (int col = 0; col < b; ++col) {
+    iters[col] = isc[col];
+    const int s = isc[(size_t)b + col];
+    status[col] = s == kCgActive ? RBL_SOLVE_MAX_ITER : s;
+    const double bb = dots[col], rr = dots[(size_t)b + col];
+    resid[col] = bb > 0.0 ? std::sqrt(rr / bb) : std::sqrt(rr);
+    if (coef)
+      for (int j = 0; j < max_iter; ++j)
+        for (int q = 0; q < 2; ++q)
+          coef[(size_t)col * 2 * max_iter + 2 * j + q] = hist[((size_t)2 * j + q) * b + col];
+  }
+  return RBL_OK;
+}
+
+// Diagnostics (tools/bench_solve.py): hipEvent time per pass of the three row passes of one CG
+// iteration on scratch blocks of len_rows x b doubles — ms[0] the dot pass, ms[1] the update pass
+// (each with its reduce_slab), ms[2] the direction pass; with r > 0 the direction pass reads a V of
+// lr_padded_width(r) columns and ms[2] includes the projection w = V^T r and c = dv o w before it.
+// All columns stay active; alpha = beta = 0 keeps the values bounded over any number of repeats.
+int rbl_bench_cg_pass(rbl_ctx* ctx, int64_t len_rows, int b, int r, int reps, double* ms) {
+  if (!ctx || len_rows < 1 || b < 1 || b > RBL_MAX_BLOCK || r < 0 || r > 32 || reps < 1 || !ms)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_cg_pass: bad arguments");
+  HIPC(hipSetDevice(ctx->device));
+  const int rp = r > 0 ? lr_padded_width(r) : 0;
+  CgBufs g;
+  CHK(cg_alloc(ctx, g, len_rows, b, rp, 0));
+  DevBuf<double> V, dv;
+  if (rp > 0) {
+    HIPC(V.alloc((size_t)len_rows * rp));
+    HIPC(hipMemsetAsync(V, 0, (size_t)len_rows * rp * sizeof(double), ctx->stream));
+    HIPC(dv.alloc((size_t)rp));
+    HIPC(hipMemsetAsync(dv, 0, (size_t)rp * sizeof(double), ctx->stream));
+  }
+  const CgScalars sc = g.scalars(b);
+  std::vector<int> act((size_t)b, kCgActive);
+  HIPC(hipMemcpyAsync(sc.status, act.data(), (size_t)b * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  double *w = g.wc, *c = rp > 0 ? g.wc + (size_t)rp * b : nullptr;
+  hipStream_t st = ctx->stream;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  auto dot = [&] { cg_dot(len_rows, b, g.P, g.W, 0.5, g.part, g.dots, st); };
+  auto update = [&] { cg_update(len_rows, b, g.X, g.R, g.P, g.W, 0.5, sc, g.part, g.dots, st); };
+  auto dir = [&] {
+    if (rp > 0) {
+      lr_project(len_rows, b, rp, V, g.R, g.lrpart, w, st);
+      cg_small(rp, b, dv, w, c, st);
+    }
+    cg_dir(len_rows, b, rp, g.R, g.P, V, c, sc, st);
+  };
+  int stt = RBL_OK;
+  auto timed = [&](auto&& fn, double* out) {
+    fn();  // warm-up
+    if (hipEventRecord(e0, st) != hipSuccess) stt = RBL_ERR_HIP;
+    for (int q = 0; q < reps; ++q) fn();
+    if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) stt = RBL_ERR_HIP;
+    float el = 0.f;
+    if (hipEventElapsedTime(&el, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) stt = RBL_ERR_HIP;
+    *out = (double)el / reps;
+  };
+  timed(dot, &ms[0]);
+  timed(update, &ms[1]);
+  timed(dir, &ms[2]);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (stt != RBL_OK) return fail(ctx, stt, "rbl_bench_cg_pass: a HIP call failed");
   return RBL_OK;
 }
 

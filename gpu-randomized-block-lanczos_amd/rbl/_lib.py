@@ -61,6 +61,10 @@ RBL_MATRIX_FORMAT_KERNOP = 6
 # rbl_cheb_diag: the block drawn when X is NULL
 RBL_PROBE_GAUSS = 0
 RBL_PROBE_SIGN = 1
+# rbl_solve: the per-column status
+RBL_SOLVE_CONVERGED = 0
+RBL_SOLVE_MAX_ITER = 1
+RBL_SOLVE_NOT_POSDEF = 2
 # rbl_thick_restart: the most columns keep_blocks * b the in-place compression keeps
 RBL_COMPRESS_MAX_COLS = 512
 
@@ -139,6 +143,11 @@ SIGNATURES = {
     "rbl_set_lowrank": (C.c_int, [_p, C.c_int, _pd, _pd]),
     "rbl_get_lowrank": (C.c_int, [_p, C.POINTER(C.c_int), _pd, _pd]),
     "rbl_bench_lowrank_pass": (C.c_int, [_p, _i64, C.c_int, C.c_int, C.c_int, _pd, _pd]),
+    "rbl_set_precond_lowrank": (C.c_int, [_p, C.c_int, _pd, _pd]),
+    "rbl_clear_precond": (C.c_int, [_p]),
+    "rbl_solve": (C.c_int, [_p, C.c_int, _pd, _pd, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                            _pi32, _pi32, _pd, _pd]),
+    "rbl_bench_cg_pass": (C.c_int, [_p, _i64, C.c_int, C.c_int, C.c_int, _pd]),
     "rbl_ritz_project": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd]),
     "rbl_ritz_finish": (C.c_int, [_p, C.c_int, _pd, _pd, _pd, _pd]),
     "rbl_ritz_finish_cols": (C.c_int, [_p, C.c_int, C.c_int, _pd, _pd, _pd, _pd]),

@@ -367,11 +367,23 @@ def _inverse(x):
 
 class GPModel(_KernelFit):
     """A fitted Gaussian-process regression (``gp_fit``): alpha = (K + noise I)^-1 y (n x t), the
-    spectrum bounds (lo, hi) and the Chebyshev coefficients of 1 / x on them that every solve uses."""
+    spectrum bounds (lo, hi) and the Chebyshev coefficients of 1 / x on them that every solve uses —
+    or, fitted with solver="cg", neither (both None): every solve is then batched CG with the fit's
+    tol, max_iter and spectral preconditioner ``precond`` = (V, dv) or None."""
 
-    def __init__(self, K, shift, device, y, alpha, bounds, coef, tol, vec):
+    def __init__(self, K, shift, device, y, alpha, bounds, coef, tol, vec, solver="chebyshev", precond=None,
+                 max_iter=1000):
         super().__init__(K, shift, device)
         self.y, self.alpha, self.bounds, self.coef, self.tol, self._vec = y, alpha, bounds, coef, tol, vec
+        # solver="cg": every solve is ``Context.solve`` (bounds and coef are None); precond: its (V, dv)
+        self.solver, self.precond, self.max_iter = solver, precond, max_iter
+
+    def _cg_solve(self, ctx, C):
+        """(K + noise I)^-1 C by the fit's CG (the preconditioner already set on ctx)."""
+        from .solve import solve_on
+        S, info = solve_on(ctx, C, tol=self.tol, max_iter=self.max_iter)
+        _cg_check("GPModel.predict", info, self.max_iter)
+        return S
 
     @property
     def noise(self) -> float:
@@ -390,7 +402,10 @@ class GPModel(_KernelFit):
         RBL_MAX_BLOCK points), S = (K + noise I)^-1 C by the series of the fit, var = kappa(z, z) -
         colsum(C o S).  The series is accurate to ``tol`` relative to 1 / lo, so a variance is
         accurate to about tol kappa(z, z) hi / lo; values below that can come out slightly negative
-        and are returned clipped at 0."""
+        and are returned clipped at 0.  A model fitted with solver="cg" solves S = (K + noise I)^-1 C
+        by batched CG instead (the fit's tol, max_iter and preconditioner; chunks of 64 columns): each
+        column then meets |c - (K + noise I) s| <= tol |c|, so a variance is accurate to about
+        tol |c|^2 / noise."""
         Zs = self._points("GPModel.predict", Z)
         m = Zs.shape[0]
         with Context(self.device) as ctx:
@@ -399,11 +414,18 @@ class GPModel(_KernelFit):
             mean = mean[:, 0] if self._vec else mean
             if not return_var:
                 return mean
-            ctx.set_filter_series(self.bounds[0], self.bounds[1], self.coef)
+            if self.solver == "cg":
+                if self.precond is not None:
+                    ctx.set_preconditioner(*self.precond)
+            else:
+                ctx.set_filter_series(self.bounds[0], self.bounds[1], self.coef)
             var = self._prior_var(Zs)
             for c0 in range(0, m, _lib.RBL_MAX_BLOCK):
                 Zc = Zs[c0:c0 + _lib.RBL_MAX_BLOCK]
                 C = ctx.kernel_cross(Zc, np.eye(Zc.shape[0]), trans=True)
+                if self.solver == "cg":
+                    var[c0:c0 + C.shape[1]] -= (C * self._cg_solve(ctx, C)).sum(axis=0)
+                    continue
                 for j0 in range(0, C.shape[1], _SOLVE_CHUNK):
                     Cj = C[:, j0:j0 + _SOLVE_CHUNK]
                     var[c0 + j0:c0 + j0 + Cj.shape[1]] -= (Cj * ctx.apply_filter(Cj)).sum(axis=0)
@@ -414,11 +436,20 @@ class GPModel(_KernelFit):
         log 2 pi, summed over the t columns of y.  The log det term is a Hutchinson estimate over
         nvec Gaussian probes (``rbl.logdet`` on the bounds of the fit); stderr is its standard error
         carried to the result (t / 2 times the estimator's) — the data-fit term is exact to the
-        solver's tolerance."""
+        solver's tolerance.  A model fitted with solver="cg" has no bounds: its log det term is
+        stochastic Lanczos quadrature on the CG coefficients of nvec Rademacher probes drawn on the
+        host from ``seed`` (``rbl.logdet_lanczos``: runs to the fit's tol or min(n, max_iter, 4096)
+        iterations, unpreconditioned), with the standard error over those probes."""
         from .funm import _trace_on
         n, t = self.y.shape
         with Context(self.device) as ctx:
             ctx.set_matrix(self.K)
+            if self.solver == "cg":
+                from .solve import MAX_COEF_ITER, logdet_lanczos_on
+                ld, err = logdet_lanczos_on(ctx, nvec, 0.0, seed, max(self.tol, 1e-12),
+                                            min(n, self.max_iter, MAX_COEF_ITER))
+                fit = float(np.sum(self.y * self.alpha))
+                return -0.5 * fit - 0.5 * t * ld - 0.5 * n * t * np.log(2.0 * np.pi), 0.5 * t * err
             ld, err = _trace_on(ctx, np.log, self.bounds[0], self.bounds[1], nvec, None, max(self.tol, 1e-12),
                                 seed, None)
         fit = float(np.sum(self.y * self.alpha))
@@ -428,19 +459,46 @@ class GPModel(_KernelFit):
 _SOLVE_CHUNK = 64   # columns per rbl_apply_filter call, as rbl.funm.APPLY_CHUNK
 
 
+def _cg_check(what, info, max_iter):
+    """A CG solve of K + noise I must converge: RBLError for a column that is not positive definite,
+    a warning for one that reached max_iter."""
+    if np.any(info.status == _lib.RBL_SOLVE_NOT_POSDEF):
+        raise _lib.RBLError(_lib.RBL_ERR_NUMERIC, f"{what}: K + noise I is not positive definite in floating point")
+    slow = np.flatnonzero(info.status == _lib.RBL_SOLVE_MAX_ITER)
+    if slow.size:
+        import warnings
+        warnings.warn(f"{what}: {slow.size} column(s) reached max_iter = {max_iter} (largest residual "
+                      f"{float(info.residual[slow].max()):.2e})", RuntimeWarning, stacklevel=3)
+
+
 def gp_fit(X, y, *, kind: str = "rbf", gamma: float = 1.0, noise: float, coef0: float = 0.0, degree: int = 3,
-           tol: float = 1e-10, bounds=None, device: int = 0) -> GPModel:
+           tol: float = 1e-10, bounds=None, device: int = 0, solver: str = "chebyshev", precond_rank: int = 0,
+           max_iter: int = 1000) -> GPModel:
     """Gaussian-process regression on the n points X with targets y (n, or n x t for t outputs) and
     observation noise variance ``noise`` > 0: alpha = (K + noise I)^-1 y by ``apply_function`` with
     f = 1 / x, K never formed; ``predict`` and ``log_marginal_likelihood`` on the model.
 
     The solver is ``apply_function``'s Chebyshev series of 1 / x on [lo, hi] and has its limits: the
     degree grows like sqrt(hi / lo) log(1 / tol), so it suits K + noise I of moderate condition number
-    (noise not many orders below the largest eigenvalue, at most n for the radial kernels); there is
-    no Krylov solver here.  bounds=(lo, hi) must enclose the spectrum of K + noise I with lo > 0.
+    (noise not many orders below the largest eigenvalue, at most n for the radial kernels); solver="cg"
+    below is the Krylov alternative.  bounds=(lo, hi) must enclose the spectrum of K + noise I with lo > 0.
     None: for the positive semi-definite kernels (rbf, laplace, poly with coef0 >= 0) lo = 0.99
     noise; hi = 1.01 max((K + noise I) 1) for the two radial kernels (entries >= 0: a row sum bounds
-    the spectrum), else the estimate of ``estimate_spectrum``."""
+    the spectrum), else the estimate of ``estimate_spectrum``.
+
+    solver="cg": alpha comes from ``Context.solve`` (batched conjugate gradients to |r| <= tol |y|, at
+    most max_iter iterations) and no spectrum bounds are computed or needed; ``predict(return_var=True)``
+    solves its columns the same way and ``log_marginal_likelihood`` uses Lanczos quadrature on the CG
+    coefficients (``rbl.logdet_lanczos``).  precond_rank=r (1..32, solver="cg" only): the r leading
+    eigenpairs of K + noise I are computed first (``lanczos``, block size r) and deflated by
+    ``spectral_preconditioner`` — the iteration count then follows the spectrum below them.  A status
+    other than converged raises RBLError (not positive definite) or warns (max_iter reached)."""
+    if solver not in ("chebyshev", "cg"):
+        raise ValueError('gp_fit: solver must be "chebyshev" or "cg"')
+    if isinstance(precond_rank, bool) or not isinstance(precond_rank, (int, np.integer)) or not 0 <= precond_rank <= 32:
+        raise ValueError("gp_fit: precond_rank must be an integer in [0, 32]")
+    if precond_rank and solver != "cg":
+        raise ValueError('gp_fit: precond_rank needs solver="cg"')
     if isinstance(noise, bool) or not np.isscalar(noise) or not np.isfinite(noise) or not noise > 0:
         raise ValueError("gp_fit: noise must be a finite number > 0")
     if not np.isscalar(tol) or not 0 < tol < 1:
@@ -454,6 +512,23 @@ def gp_fit(X, y, *, kind: str = "rbf", gamma: float = 1.0, noise: float, coef0: 
         raise ValueError(f"gp_fit: y must have n = {K.n} rows")
     if not np.all(np.isfinite(y)):
         raise ValueError("gp_fit: y has a non-finite entry")
+    if solver == "cg":
+        if bounds is not None:
+            raise ValueError('gp_fit: bounds belong to solver="chebyshev" (CG needs none)')
+        if precond_rank > K.n:
+            raise ValueError(f"gp_fit: precond_rank = {precond_rank} exceeds n = {K.n}")
+        from .solve import solve_on, spectral_preconditioner
+        precond = None
+        with Context(device) as ctx:
+            ctx.set_matrix(K)
+            if precond_rank:
+                lam, V, _ = _run(ctx, int(precond_rank), int(precond_rank), None, None, 0)
+                V, dv = spectral_preconditioner(lam, V)
+                precond = (np.asfortranarray(V), dv)
+                ctx.set_preconditioner(*precond)
+            alpha, info = solve_on(ctx, y, tol=tol, max_iter=max_iter)
+        _cg_check("gp_fit", info, max_iter)
+        return GPModel(K, shift, device, y, alpha, None, None, float(tol), vec, "cg", precond, int(max_iter))
     from .density import _bounds
     from .funm import apply_function, cheb_fit
     with Context(device) as ctx:

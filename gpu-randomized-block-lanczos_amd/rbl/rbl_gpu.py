@@ -381,6 +381,69 @@ class Context:
                                                dptr(um)), "rbl_bench_lowrank_pass")
         return float(pm[0]), float(um[0])
 
+    def set_preconditioner(self, V, dv=None) -> None:
+        """The preconditioner of ``solve``, M^-1 = I + V diag(dv) V^T (rbl_set_precond_lowrank): V
+        n x r with orthonormal columns, 1 <= r <= 32, dv its r entries (all > -1), both copied to the
+        device in buffers of their own (a ``set_lowrank`` update may be set too).  ``None`` clears it
+        (rbl_clear_precond); setting a matrix clears it as well."""
+        if V is None:
+            self._check(lib.rbl_clear_precond(self._h), "rbl_clear_precond")
+            return
+        n, r0, r1, _ = self.matrix_info()
+        V = np.asarray(V, dtype=np.float64)
+        dv = np.asarray(dv, dtype=np.float64) if dv is not None else None
+        if V.ndim == 1:
+            V = V.reshape(-1, 1)
+        if V.ndim != 2 or V.shape[0] != r1 - r0:
+            raise ValueError(f"set_preconditioner: V must have {r1 - r0} rows")
+        r = V.shape[1]
+        if dv is None or dv.reshape(-1).shape != (r,):
+            raise ValueError(f"set_preconditioner: dv must have {r} entries")
+        if r < 1:
+            raise ValueError("set_preconditioner: V has no columns (None clears the preconditioner)")
+        V = np.asfortranarray(V)
+        dv = np.ascontiguousarray(dv.reshape(-1))
+        self._check(lib.rbl_set_precond_lowrank(self._h, r, dptr(V), dptr(dv)), "rbl_set_precond_lowrank")
+
+    def solve(self, B, shift: float = 0.0, tol: float = 1e-10, max_iter: int = 1000, x0=None,
+              check_every: int = 10, coef: bool = False):
+        """(X, iters, status, resid[, alpha, beta]) of (Op + shift I) X = B by batched preconditioned
+        CG on the device (rbl_solve): B n x b with b <= RBL_MAX_BLOCK, every column its own recurrence
+        and one shared product per iteration.  Per column: iters, status (0 converged to |r| <= tol
+        |b|, 1 max_iter reached, 2 not positive definite) and resid, the true |b - (Op + shift) x| /
+        |b| of the returned x.  x0: a starting guess of B's shape.  coef=True (max_iter <= 4096) also
+        returns the CG coefficients alpha, beta as max_iter x b arrays, zero past a column's iters
+        (``rbl.cg_tridiag``).  The preconditioner is the one of ``set_preconditioner``."""
+        n, r0, r1, _ = self.matrix_info()
+        B = np.asfortranarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != r1 - r0 or B.shape[1] < 1:
+            raise ValueError(f"solve: B must be {r1 - r0} x b")
+        b, max_iter = B.shape[1], int(max_iter)
+        if x0 is None:
+            X = np.zeros(B.shape, order="F")
+        else:
+            X = np.array(x0, dtype=np.float64, order="F")
+            if X.shape != B.shape:
+                raise ValueError("solve: x0 must have the shape of B")
+        iters = np.zeros(b, dtype=np.int32)
+        status = np.zeros(b, dtype=np.int32)
+        resid = np.zeros(b)
+        hist = np.zeros((2 * max(max_iter, 1), b), order="F") if coef else None
+        self._check(lib.rbl_solve(self._h, b, dptr(B), dptr(X), float(shift), float(tol), max_iter,
+                                  int(check_every), int(x0 is not None), i32ptr(iters), i32ptr(status),
+                                  dptr(resid), dptr(hist)), "rbl_solve")
+        if coef:
+            return X, iters, status, resid, hist[0::2].copy(), hist[1::2].copy()
+        return X, iters, status, resid
+
+    def bench_cg_pass(self, rows: int, b: int, r: int = 0, reps: int = 20):
+        """(dot_ms, update_ms, dir_ms) per pass of the three row passes of one CG iteration on scratch
+        blocks of rows x b (rbl_bench_cg_pass); r > 0: with a rank-r preconditioner."""
+        ms = np.zeros(3)
+        self._check(lib.rbl_bench_cg_pass(self._h, int(rows), int(b), int(r), int(reps), dptr(ms)),
+                    "rbl_bench_cg_pass")
+        return tuple(float(v) for v in ms)
+
     def left_vectors(self, V: np.ndarray, sigma) -> np.ndarray:
         """U = B V diag(1 / sigma) (images.jl:24), m x k, from V (n x k) and the singular values
         (with a shift set: C V diag(1 / sigma))."""

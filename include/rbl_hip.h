@@ -573,6 +573,49 @@ int rbl_get_lowrank(rbl_ctx* ctx, int* r_out, double* P_out, double* S_out);
 int rbl_bench_lowrank_pass(rbl_ctx* ctx, int64_t rows, int b, int r, int reps, double* project_ms,
                            double* update_ms);
 
+/* Preconditioned conjugate gradients: (Op + shift I) X = B for a symmetric positive definite
+ * Op + shift I, Op whatever rbl_apply applies (sparse, dense or kernel matrix, with the update of
+ * rbl_set_lowrank when one is set).  The b columns run their own Hestenes-Stiefel recurrence and
+ * share one product per iteration; every per-column scalar stays on the device, a column is frozen
+ * on the device once |r| <= tol |b| (its x is not stored again), and the host only reads the count
+ * of active columns every check_every iterations — the returned bits do not depend on check_every.
+ * All sums run in a fixed order, no atomics: two calls give the same bits.
+ *
+ * rbl_set_precond_lowrank: the preconditioner M^-1 = I + V diag(dv) V^T, V n x r column-major with
+ *   orthonormal columns (not checked), 1 <= r <= 32, dv[i] > -1 finite; both copied to the device,
+ *   in buffers of their own (an rbl_set_lowrank update may be set at the same time).  Replaces an
+ *   earlier one; rbl_clear_precond, setting any matrix and rbl_free drop it.  RBL_ERR_INVALID
+ *   (several ranks, a rectangular B, r outside [1, 32], a NULL or non-finite argument) and
+ *   RBL_ERR_STATE (no matrix) leave the context as it was.
+ * rbl_solve: B and X n x b column-major on the host, 1 <= b <= RBL_MAX_BLOCK.  use_x0 != 0: X holds
+ *   the starting guess (one extra product forms r = b - (Op + shift) x0); else x0 = 0.  Stops when
+ *   every column is frozen or after max_iter iterations (1 .. 65535; with coef at most 4096).  Per
+ *   column: iters, status (RBL_SOLVE_CONVERGED; RBL_SOLVE_MAX_ITER; RBL_SOLVE_NOT_POSDEF: p^T (Op +
+ *   shift) p <= 0 or not finite — the column keeps the x it had, and the call still returns RBL_OK),
+ *   resid = |b - (Op + shift I) x| / |b| of the returned x, from one final product (|b| = 0: the
+ *   absolute norm; a zero column returns x = 0, converged, 0 iterations).  coef (NULL or 2 max_iter b
+ *   doubles): column c's alpha_j at coef[c * 2 max_iter + 2 j] and beta_j one further, j < iters[c],
+ *   zero beyond — the Lanczos tridiagonal of (Op + shift I, b_c) (rbl.cg_tridiag).
+ *   Timed under "AQ" (the products) and "3-term" (the row passes); while RBL_OPT_TIMERS is on the
+ *   host looks at the active count at least every 64 iterations, so the timing events in flight stay
+ *   bounded whatever check_every is.
+ *   Limits (before any allocation; the context stays usable): RBL_ERR_INVALID for b, max_iter or
+ *   check_every (>= 1) out of range, tol outside (0, 1), a non-finite shift, a NULL pointer, several
+ *   ranks or a rectangular B; RBL_ERR_STATE without a matrix or while the run has the fp32 basis.
+ *   Device memory: 5 blocks of n x b doubles for the call. */
+#define RBL_SOLVE_CONVERGED  0
+#define RBL_SOLVE_MAX_ITER   1
+#define RBL_SOLVE_NOT_POSDEF 2
+int rbl_set_precond_lowrank(rbl_ctx* ctx, int r, const double* V, const double* dv);
+int rbl_clear_precond(rbl_ctx* ctx);
+int rbl_solve(rbl_ctx* ctx, int b, const double* B, double* X, double shift, double tol, int max_iter,
+              int check_every, int use_x0, int* iters, int* status, double* resid, double* coef);
+/* Diagnostics: ms[0..2] = the time per pass (hipEvents, mean over `reps` after one warm-up) of the
+ * dot pass, the update pass (each with its partial-sum reduction) and the direction pass of one CG
+ * iteration on scratch blocks of len_rows x b doubles; r > 0: with a preconditioner of rank r, the
+ * direction pass then includes the projection V^T r. */
+int rbl_bench_cg_pass(rbl_ctx* ctx, int64_t len_rows, int b, int r, int reps, double* ms);
+
 /* Rayleigh-Ritz on A with true residuals (also without a filter).
  * rbl_ritz_project: V = [Q_1..Q_nblocks] S (S: (nblocks*b) x k column-major, host; orthonormal
  *   columns) and W = A V (the plain operator, never the filter; with rbl_set_lowrank A + P S P^T)

@@ -22,6 +22,7 @@
 #   D, V, r = RBL_gpu_filtered(A, k, b; which = :SA, degree = 8)   # the k smallest (or :LA largest)
 #                                        # pairs through a Chebyshev filter, r = ||A v - D v||
 #   c, (lo, hi) = RBL_gpu_eigcount(A, x0, x1)     # expected number of eigenvalues in [x0, x1] (KPM)
+#   X, iters, status, resid = RBL_gpu_solve(A, B; shift = 0.5)   # (A + shift I) X = B by batched CG
 #
 # Untested here: Julia is not installed in the build container (SURVEY §8(c)).  Every ccall
 # below is checked against include/rbl_hip.h by tests/test_julia_binding.py (argument count
@@ -357,6 +358,57 @@ function RBL_gpu_kernel_predict(X::Matrix{Float64}, W::Matrix{Float64}, Z::Matri
     try
         set_matrix!(ctx, KernelPoints(X, kind, gamma, coef0, degree, scale, 0.0))
         return kernel_cross(ctx, Z, W)
+    finally
+        ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
+    end
+end
+
+# (Op + shift I) X = B by batched preconditioned conjugate gradients on the operator a context holds
+# (rbl_solve; with set_lowrank! the updated one): B n x b, every column its own recurrence to
+# |r| <= tol |b| or max_iter iterations.  precond = (V, dv): M^-1 = I + V diag(dv) V^T
+# (rbl_set_precond_lowrank; V n x r orthonormal, r <= 32), set on the context before the solve and
+# kept there; without the keyword the context's preconditioner is left as it is (clear_precond!
+# drops it), as Context.solve does in Python.  x0: a starting guess of B's shape.
+# Returns X, iters, status (0 converged, 1 max_iter reached, 2 not positive definite) and the true
+# relative residuals, per column.
+function solve(ctx::Ptr{Cvoid}, B::Matrix{Float64}; shift::Float64 = 0.0, tol::Float64 = 1e-10,
+               max_iter::Int = 1000, x0 = nothing, precond = nothing, check_every::Int = 10)
+    n, b = size(B)
+    if precond !== nothing
+        V, dv = precond
+        size(V, 1) == n && size(V, 2) == length(dv) || throw(ArgumentError("solve: V must be n x length(dv)"))
+        rbl_check(ctx, ccall((:rbl_set_precond_lowrank, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}),
+                             ctx, Cint(size(V, 2)), V, dv), "rbl_set_precond_lowrank")
+    end
+    X = x0 === nothing ? zeros(Float64, n, b) : Matrix{Float64}(x0)
+    size(X) == (n, b) || throw(ArgumentError("solve: x0 must have the shape of B"))
+    iters = zeros(Cint, b)
+    status = zeros(Cint, b)
+    resid = zeros(Float64, b)
+    rbl_check(ctx, ccall((:rbl_solve, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Cint, Cint,
+                          Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}),
+                         ctx, Cint(b), B, X, shift, tol, Cint(max_iter), Cint(check_every),
+                         Cint(x0 === nothing ? 0 : 1), iters, status, resid, C_NULL), "rbl_solve")
+    return X, iters, status, resid
+end
+
+# Drops the preconditioner of `solve` from the context (rbl_clear_precond).
+function clear_precond!(ctx::Ptr{Cvoid})
+    rbl_check(ctx, ccall((:rbl_clear_precond, librbl_hip), Cint, (Ptr{Cvoid},), ctx), "rbl_clear_precond")
+end
+
+# x = (A + shift I) \ B on the GPU for a symmetric positive definite A + shift I (sparse, dense or
+# KernelPoints); update = (P, S): of A + P S P^T.  One context: set_matrix!, solve, free.
+function RBL_gpu_solve(A::Union{SparseMatrixCSC{Float64},Matrix{Float64},KernelPoints}, B::Matrix{Float64};
+                       shift::Float64 = 0.0, tol::Float64 = 1e-10, max_iter::Int = 1000, x0 = nothing,
+                       update = nothing, precond = nothing, device::Int = 0)
+    ctx = rbl_context(device)
+    try
+        set_matrix!(ctx, A)
+        update === nothing || set_lowrank!(ctx, update[1], update[2])
+        return solve(ctx, B; shift = shift, tol = tol, max_iter = max_iter, x0 = x0, precond = precond)
     finally
         ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
     end
