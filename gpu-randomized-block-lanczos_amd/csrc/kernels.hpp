@@ -555,6 +555,15 @@ void chol_step(const double* G, int b, int64_t nglobal, int mode, double* R, dou
 void copy_small(const double* src, double* dst, int64_t len, hipStream_t s, const int* skip = nullptr);
 // C = C Rinv (b x b, Rinv upper triangular) unless *skip (k_cloc_rinv)
 void cloc_rinv(double* C, const double* Rinv, int b, const int* skip, hipStream_t s);
+// C = (C R1inv) R2inv, both upper triangular, b <= 32 (k_cloc_rinv2)
+void cloc_rinv2(double* C, const double* R1inv, const double* R2inv, int b, hipStream_t s);
+// gate[0] = 1 iff (Q^T U) R^-1 is as good as the Gram Q^T (U R^-1) to eps tau: *need3 == 0 and
+// max_c sum_j |R[:, j]| |Rinv[j][c]| <= tau; gate[1] = !gate[0].  b <= 32 (k_cloc_gate)
+void cloc_gate(const double* R, const double* Rinv, int b, const int* need3, double tau, int* gate,
+               hipStream_t s);
+// G -= Cm^T Ci with D = [Ci | Cm] (nW b x 2b row-major), b <= 256; a fixed summation order
+// (k_cloc_sub)
+void cloc_sub(double* G, const double* D, int nW, int b, hipStream_t s);
 // dst = src^T (b x b row-major).
 void transpose_small(const double* src, double* dst, int b, hipStream_t s);
 // stash = [A_i (b x b) | R_tot (b x b) | 4 int flags], Bprev = R_tot, flags cleared (k_stash)

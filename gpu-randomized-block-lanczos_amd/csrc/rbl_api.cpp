@@ -227,7 +227,7 @@ struct RunBufs {
   DevBuf<double> d_slab;
   DevBuf<double> d_C;        // Gram result (<= (max_blocks)*b x 2b)
   DevBuf<double> d_small;    // R, Rinv, Rtot, Bprev, Ai, G (b x b each)
-  DevBuf<int> d_flags;       // [need3, skip3, status0, status1]
+  DevBuf<int> d_flags;       // [need3, skip3, status0, status1, cloc derived, cloc direct]
   PinBuf<double> h_pin;      // pinned staging: Ai, Rtot (2 b x b)
   PinBuf<double> h_hist;     // rbl_step_async stash: per step i, Ai and Rtot (2 b x b) and the
                              //   step's 4 flags (2 doubles' room): stash_rec(b) doubles each
@@ -394,6 +394,11 @@ struct rbl_ctx : rbl::api::MatrixBufs, rbl::api::RunBufs, rbl::api::CtxBufs {
   // step cloc_step - 1 or by the last partial-reorth update of step cloc_step; 0: none
   int cloc_step = 0;
   bool cloc_final = false;    // formed after this step's reorth (valid whatever its flags)
+  // RBL_OPT_CLOC_DERIVE: S_CLOC from the 3-term pass's M = Q_i^T U' and CholQR's factors, and
+  // through a block-CGS partial reorth as G - Cm^T Ci (cloc_derive_on)
+  bool cloc_derive = true;
+  int cloc_src = 0;           // who formed S_CLOC: 0 a Gram pass, 1 the 3-term pass, 2 G - Cm^T Ci
+  bool plan_all_resident = false;  // this run was started with RBL_OPT_DEVICE_BLOCKS = 0
   std::vector<int> step_flags;  // part_reorth flags per step (the fusion's schedule guess)
   double stage_ms[RBL_NUM_STAGES] = {0};
   // collectives issued by this rank since the last reset (rbl_comm_stats): all-reduce calls and
@@ -1538,8 +1543,11 @@ Panels pan2(const double* p0, const double* p1, int w) {
 // step's local-reorth Gram
 // (S_CLOC follows S_G: CholQR's pass-3 Gram and the next step's local-reorth Gram share one
 // all-reduce of 2 b^2)
-enum { S_R = 0, S_RINV, S_RTOT, S_BPREV, S_AI, S_G, S_CLOC, S_BT, S_CHS0, S_CHS1, S_RINV1, S_NSMALL };
+// S_CX precedes S_G: with RBL_OPT_CLOC_DERIVE the pass-3 Gram travels with the direct cross Gram
+// of an ill-conditioned step instead (tsqr), while S_CLOC holds the derived coefficient
+enum { S_R = 0, S_RINV, S_RTOT, S_BPREV, S_AI, S_CX, S_G, S_CLOC, S_BT, S_CHS0, S_CHS1, S_RINV1, S_NSMALL };
 static_assert(S_CLOC == S_G + 1, "tsqr all-reduces [S_G | S_CLOC] as one 2 b^2 buffer");
+static_assert(S_G == S_CX + 1, "tsqr all-reduces [S_CX | S_G] as one 2 b^2 buffer");
 double* smallp(rbl_ctx* ctx, int which) { return ctx->d_small + (int64_t)which * ctx->b * ctx->b; }
 
 int tsmm_checked(rbl_ctx* ctx, const PanelRun& X, const double* C, int ldc, const Panels& Y,
@@ -1954,6 +1962,17 @@ int lock_reorth(rbl_ctx* ctx, double* X) {
   return RBL_OK;
 }
 
+// RBL_OPT_CLOC_DERIVE applies to this run: options and plan state only, so every rank (and every
+// run of a pair that differs in the SpMM's route alone) decides the same.  Block CGS and an
+// all-resident basis are asked of both routes: the derivation through the partial reorth needs
+// them, and with either unmet the run keeps the bits of the option-off routes.  On several ranks
+// "all resident" must follow from the option (RBL_OPT_DEVICE_BLOCKS = 0): the automatic plan
+// looks at each rank's own free memory, and the routes differ in their all-reduces.
+bool cloc_derive_on(const rbl_ctx* ctx) {
+  return ctx->cloc_derive && ctx->basis_bits == 64 && rowgram_ok(ctx->b) && (ctx->fuse & 3) == 3 &&
+         ctx->reorth_order == 0 && !spilled(ctx) && (ctx->nranks == 1 || ctx->plan_all_resident);
+}
+
 // Reorth of the pair (Q_i, Q_{i-1}) = slots (i-1, i-2) of the fp64 basis:
 //   flags bit 1: against the locked vectors, Q_{i-1} then Q_i (restarted.jl:54-55);
 //   flags bit 0: against Q_1..Q_{i-2} (RBL_gpu.jl:59-81; block CGS, or the reference's
@@ -1976,7 +1995,14 @@ int reorth_pair(rbl_ctx* ctx, int i, int flags) {
     // (RBL_OPT_FUSE bit 1; the update's 64-column fast path: b = 32)
     // (the same decision on every rank: the all-reduce below pairs up; a rank where the fast
     // path does not apply — too few rows, slab too small — forms its share with the Gram kernel)
-    const bool xg = (ctx->fuse & 2) && b == 32;
+    // RBL_OPT_CLOC_DERIVE: S_CLOC holds G = Q_{i-1}^T Q_i of the pair as it stands (formed with
+    // Q_i, nothing touched the pair since), and block CGS is about to form C = W^T [Q_i | Q_{i-1}]
+    // = [Ci | Cm] over all of W: afterwards Q'_{i-1}^T Q'_i = G - Cm^T Ci + Cm^T (W^T W - I) Ci,
+    // the last term dropped (|Cm| |Ci| |W^T W - I|, far below the rounding of G).  The update
+    // then runs plain: no cross-Gram epilogue, no partials, no all-reduce.
+    const bool derive = cloc_derive_on(ctx) && b == 32 && ctx->cloc_step == i && !ctx->cloc_final &&
+                        !((flags & 2) && ctx->nlock > 0) && nres == nW;
+    const bool xg = (ctx->fuse & 2) && b == 32 && !derive;
     const int xg_parts = tsmm44_xg_grid(ctx->nloc);
     const bool xslab_ok = (size_t)(xg_parts + reduce_scratch_splits(xg_parts)) * b * b <= ctx->slab_elems;
     int xgrid = 0;
@@ -2024,6 +2050,13 @@ int reorth_pair(rbl_ctx* ctx, int i, int flags) {
       CHK(allreduce(ctx, smallp(ctx, S_CLOC), (size_t)b * b));
       ctx->cloc_step = i;
       ctx->cloc_final = true;
+      ctx->cloc_src = 0;
+    }
+    if (derive) {  // d_C still holds [Ci | Cm], all-reduced by the Gram
+      cloc_sub(smallp(ctx, S_CLOC), ctx->d_C, nW, b, ctx->stream);
+      HIPC(hipGetLastError());
+      ctx->cloc_final = true;
+      ctx->cloc_src = 2;
     }
   }
   return RBL_OK;
@@ -2143,7 +2176,7 @@ int rowop_ex(rbl_ctx* ctx, RowOpArgs a, double* G, double* Gx, bool reduce_x, bo
   } else {  // no rows on this rank: zero partials (the all-reduces still run on every rank)
     grid = 1;
     if (G) HIPC(hipMemsetAsync(a.slab, 0, (size_t)b * b * sizeof(double), ctx->stream));
-    if (a.Z && a.skip == nullptr)
+    if (a.Z)
       HIPC(hipMemsetAsync(a.slab2, 0, (size_t)xgrid * b * b * sizeof(double), ctx->stream));
   }
   HIPC(hipGetLastError());
@@ -2158,6 +2191,45 @@ int rowop_ex(rbl_ctx* ctx, RowOpArgs a, double* G, double* Gx, bool reduce_x, bo
   return RBL_OK;
 }
 
+// The 3-term update with both sums (RBL_OPT_CLOC_DERIVE): U' = U - Q_i A_i, S_G = U'^T U' and
+// S_CLOC = M = Q_i^T U' from one pass over Q_i and U, one all-reduce of 2 b^2.  The grid is
+// rowop's, so S_G has the bits of the pass without M.
+int rowop_3term_cloc(rbl_ctx* ctx, const double* Qi, double* U) {
+  const int b = ctx->b;
+  const int grid = rowgram_grid(ctx->nloc);
+  const size_t bb = (size_t)b * b;
+  if (2 * grid * bb > ctx->slab_elems) return fail(ctx, RBL_ERR_INVALID, "internal: row-op slab too small");
+  double* slab2 = ctx->d_slab + grid * bb;
+  if (ctx->nloc > 0) {
+    RowOpArgs a;
+    a.X = Qi;
+    a.C = smallp(ctx, S_AI);
+    a.ldc = b;
+    a.Y = U;
+    a.alpha = -1.0;
+    a.beta = 1.0;
+    a.slab = ctx->d_slab;
+    a.Z = Qi;
+    a.slab2 = slab2;
+    if (!rowgram_ex(ctx->nloc, b, a, grid, ctx->stream))
+      return fail(ctx, RBL_ERR_INVALID, "internal: unsupported fused row-op form");
+  } else {  // no rows on this rank: zero shares (the all-reduce still runs)
+    HIPC(hipMemsetAsync(ctx->d_slab, 0, 2 * grid * bb * sizeof(double), ctx->stream));
+  }
+  reduce_slab(ctx->d_slab, grid, (int64_t)bb, smallp(ctx, S_G), nullptr, ctx->stream);
+  reduce_slab(slab2, grid, (int64_t)bb, smallp(ctx, S_CLOC), nullptr, ctx->stream);
+  HIPC(hipGetLastError());
+  return allreduce(ctx, smallp(ctx, S_G), 2 * bb);
+}
+
+// RBL_OPT_CLOC_DERIVE: M's entries are sums over the same rows as the direct Gram's, so with e
+// the direct Gram's error the derived Q_i^T Q_{i+1} = (Q_i^T U') R^-1 carries at most E e from M
+// and as much again from the apply U' R^-1 (E of k_cloc_gate).  Up to E = 4 (8 e at the worst,
+// the bound tests/test_cloc_derived_host.py holds every step to) the derived one is taken,
+// beyond it — and after a shifted Cholesky — the direct one.  E is 1.1 .. 2.4 on a hash-window
+// run once the planted eigenvalues have converged, 6 .. 93 in the three steps before.
+constexpr double kClocGateTau = 4.0;
+
 // Tall-skinny QR of U (n_local x b) into Qout; B = R (b x b, upper, row-major) in S_RTOT.
 // Shifted CholQR2 (+ a third pass after a shifted first pass).  `g1_ready`: S_G already holds
 // U^T U (the fused 3-term update computed it); each apply computes the next pass's Gram in the
@@ -2166,8 +2238,11 @@ int rowop_ex(rbl_ctx* ctx, RowOpArgs a, double* G, double* Gx, bool reduce_x, bo
 // pass-2 intermediate when the shifted pass 3 runs).
 // Zloc (fp64 basis, RBL_OPT_FUSE bit 1): also form Zloc^T Q into S_CLOC — the next step's
 // local-reorth coefficient (Zloc = Q_i, Q = Q_{i+1}).
+// cloc_m (RBL_OPT_CLOC_DERIVE, with Zloc): S_CLOC holds M = Zloc^T U over all ranks and leaves as
+// Zloc^T Q = M R1^-1 R2^-1, so no pass reads Zloc — unless U is graded (k_cloc_gate, decided on
+// the device from R1): then the last pass forms Zloc^T Q2 as without cloc_m.
 int tsqr(rbl_ctx* ctx, const double* U, double* Qout, bool g1_ready = false, float* Qout32 = nullptr,
-         const double* Zloc = nullptr) {
+         const double* Zloc = nullptr, bool cloc_m = false) {
   StageScope t(ctx, RBL_STAGE_QR);
   ctx->flags_clean = false;  // the flags below start from zero only after a memset or k_stash
   const int b = ctx->b;
@@ -2193,6 +2268,9 @@ int tsqr(rbl_ctx* ctx, const double* U, double* Qout, bool g1_ready = false, flo
   if (three) {
     // 3 passes: G2 = Gram of Q1 = U R1^-1 without storing Q1; then Q = (U R1^-1) R2^-1 in
     // one pass (Q1 recomputed bit for bit) — the same bits as the 4-pass form below
+    int* gate = ctx->d_flags + 4;  // [derived, direct]
+    if (cloc_m)
+      cloc_gate(smallp(ctx, S_R), smallp(ctx, S_RINV1), b, need3, kClocGateTau, gate, ctx->stream);
     RowOpArgs a1;
     a1.X = U;
     a1.C = smallp(ctx, S_RINV1);
@@ -2202,6 +2280,7 @@ int tsqr(rbl_ctx* ctx, const double* U, double* Qout, bool g1_ready = false, flo
     CHK(rowop_ex(ctx, a1, G, nullptr, false));
     chol_step(G, b, ctx->n, 1, smallp(ctx, S_R), smallp(ctx, S_RINV), smallp(ctx, S_RTOT), need3,
               status, nullptr, ctx->stream, smallp(ctx, S_CHS0));
+    if (cloc_m) cloc_rinv2(smallp(ctx, S_CLOC), smallp(ctx, S_RINV1), smallp(ctx, S_RINV), b, ctx->stream);
     RowOpArgs a2;
     a2.X = U;
     a2.C = smallp(ctx, S_RINV1);
@@ -2211,15 +2290,30 @@ int tsqr(rbl_ctx* ctx, const double* U, double* Qout, bool g1_ready = false, flo
     a2.Y = Qout;
     a2.Y32 = Qout32;
     a2.f64flag = Qout32 ? need3 : nullptr;
-    a2.Z = Zloc;
     a2.mode = 2;
-    // Zloc: this rank's share of Zloc^T Q2 now, all-reduced below with the pass-3 Gram
-    CHK(rowop_ex(ctx, a2, nullptr, Zloc ? smallp(ctx, S_CLOC) : nullptr, Zloc != nullptr, false));
+    if (cloc_m) {
+      // one of two launches runs (device gate): the plain pass where the derived coefficient
+      // stands, the pass with the cross Gram Zloc^T Q2 (into S_CX) where U is too graded for it
+      a2.skip = gate + 1;
+      CHK(rowop_ex(ctx, a2, nullptr, nullptr, false));
+      a2.skip = gate;
+      a2.Z = Zloc;
+      CHK(rowop_ex(ctx, a2, nullptr, smallp(ctx, S_CX), true, false));
+    } else {
+      a2.Z = Zloc;
+      // Zloc: this rank's share of Zloc^T Q2 now, all-reduced below with the pass-3 Gram
+      CHK(rowop_ex(ctx, a2, nullptr, Zloc ? smallp(ctx, S_CLOC) : nullptr, Zloc != nullptr, false));
+    }
     // pass 3 only after a shifted first pass (device flag; kernels early-exit otherwise).  Its
     // Gram's all-reduce runs either way (the host does not know the flag) and carries Zloc^T Q2
-    // in the same call (S_CLOC follows S_G)
+    // in the same call (S_CLOC follows S_G; cloc_m: S_CX precedes it)
     CHK(gram(ctx, run1(Qout, b), pan1(Qout, b), G, skip3, Zloc == nullptr));
-    if (Zloc) CHK(allreduce(ctx, G, (size_t)2 * b * b));
+    if (cloc_m) {
+      CHK(allreduce(ctx, smallp(ctx, S_CX), (size_t)2 * b * b));
+      copy_small(smallp(ctx, S_CX), smallp(ctx, S_CLOC), (int64_t)b * b, ctx->stream, gate);
+    } else if (Zloc) {
+      CHK(allreduce(ctx, G, (size_t)2 * b * b));
+    }
     chol_step(G, b, ctx->n, 1, smallp(ctx, S_R), smallp(ctx, S_RINV), smallp(ctx, S_RTOT), need3,
               status, skip3, ctx->stream, smallp(ctx, S_CHS0));
     RowOpArgs a3;
@@ -2920,6 +3014,10 @@ int rbl_set_option(rbl_ctx* ctx, int option, int64_t value) {
     case RBL_OPT_FUSE:
       if (value < 0 || value > 7) return fail(ctx, RBL_ERR_INVALID, "RBL_OPT_FUSE is a 3-bit mask");
       ctx->fuse = (int)value;
+      return RBL_OK;
+    case RBL_OPT_CLOC_DERIVE:
+      if (value < 0 || value > 1) return fail(ctx, RBL_ERR_INVALID, "RBL_OPT_CLOC_DERIVE must be 0|1");
+      ctx->cloc_derive = value != 0;
       return RBL_OK;
     default: return fail(ctx, RBL_ERR_INVALID, "unknown option");
   }
@@ -3808,6 +3906,7 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
     dev_slots = std::min(dev_slots, std::max(3, g));
   }
   const bool reuse = same_shape && cur_slots == dev_slots;
+  ctx->plan_all_resident = ctx->dev_blocks_opt == 0;  // an option: the same on every rank
   ctx->nlock = 0;  // a new problem: no locked vectors
   ctx->arrow_kb = 0;
   ctx->cloc_step = 0;
@@ -3870,8 +3969,9 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   ctx->C_elems = (size_t)std::max(1, max_blocks) * b * 2 * b;
   HIPC(ctx->d_C.alloc(ctx->C_elems));
   HIPC(ctx->d_small.alloc((size_t)S_NSMALL * b * b));
-  HIPC(ctx->d_flags.alloc(4));
-  HIPC(hipMemset(ctx->d_flags, 0, 4 * sizeof(int)));
+  HIPC(hipMemset(ctx->d_small, 0, (size_t)S_NSMALL * b * b * sizeof(double)));  // (S_CX is summed before it is first written)
+  HIPC(ctx->d_flags.alloc(6));
+  HIPC(hipMemset(ctx->d_flags, 0, 6 * sizeof(int)));
   {
 #ifdef RBL_VARIANTS
     const char* e = std::getenv("RBL_STASH_COPY");  // A/B: 1 = device record + D2H copy
@@ -4133,6 +4233,10 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
     if (!have) {
       CHK(gram(ctx, run1(Qm, b), pan1(Qi, b), ctx->d_C, nullptr));
       ctx->path_stats[RBL_PATH_LOC_GRAM] += 1;
+    } else if (ctx->cloc_src == 1) {
+      ctx->path_stats[RBL_PATH_CLOC_3TERM] += 1;
+    } else if (ctx->cloc_src == 2) {
+      ctx->path_stats[RBL_PATH_CLOC_REORTH] += 1;
     }
     if (lfuse) {
       Cloc = C;
@@ -4254,6 +4358,9 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
   }
   // A_i = Q_i^T U ; U -= Q_i A_i   (RBL_gpu.jl:178-179); fused: the update pass also forms
   // U^T U, CholQR's first Gram
+  // RBL_OPT_CLOC_DERIVE: the update pass also forms M = Q_i^T U', which the QR below turns into
+  // the next step's local-reorth coefficient (on every step: no guess of that step's schedule)
+  const bool cloc_m = cloc_derive_on(ctx) && !filt && !arrow && i + 1 <= ctx->max_blocks;
   {
     StageScope t(ctx, RBL_STAGE_3TERM);
     if (ai_parts > 0) {
@@ -4263,7 +4370,9 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
     } else {
       CHK(gram(ctx, run1(Qi, b), pan1(ctx->d_U, b), smallp(ctx, S_AI), nullptr));
     }
-    if (fused)
+    if (cloc_m)
+      CHK(rowop_3term_cloc(ctx, Qi, ctx->d_U));
+    else if (fused)
       CHK(rowop(ctx, Qi, smallp(ctx, S_AI), ctx->d_U, -1.0, 1.0, smallp(ctx, S_G), nullptr,
                 direct32 ? Qi32 : nullptr));
     else
@@ -4280,11 +4389,13 @@ int step_impl(rbl_ctx* ctx, int i, int part_reorth, double* A_out, double* B_out
     // expected to run no partial reorth (the schedule repeats with period 2 in RBL_gpu.jl:164,
     // so step i + 1 is guessed from step i - 1; a wrong guess costs one pass, never bits)
     const int guess = i >= 2 ? ctx->step_flags[i - 1] : 0;
-    const bool zfuse = fused && (ctx->fuse & 3) == 3 && !modifies(i + 1, guess) && i + 1 <= ctx->max_blocks;
-    CHK(tsqr(ctx, ctx->d_U, slotp(ctx, i), fused, nullptr, zfuse ? Qi : nullptr));
-    if (zfuse) {
+    const bool zfuse = !cloc_m && fused && (ctx->fuse & 3) == 3 && !modifies(i + 1, guess) &&
+                       i + 1 <= ctx->max_blocks;
+    CHK(tsqr(ctx, ctx->d_U, slotp(ctx, i), fused, nullptr, zfuse || cloc_m ? Qi : nullptr, cloc_m));
+    if (zfuse || cloc_m) {
       ctx->cloc_step = i + 1;
       ctx->cloc_final = false;
+      ctx->cloc_src = cloc_m ? 1 : 0;
     }
   } else {  // Qg = FLOAT(Qg_d) (RBL_gpu.jl:182): the new block enters the basis rounded to fp32
     CHK(tsqr(ctx, ctx->d_U, ctx->d_Qi64, fused, slotp32(ctx, i)));

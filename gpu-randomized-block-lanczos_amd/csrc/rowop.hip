@@ -25,6 +25,10 @@
 // XG: the cross Gram Z^T Y' of another block Z (v_mfma_f64_16x16x4f64, Z read in its A layout,
 // Y' from the output stage): the next step's local-reorth coefficient Q_{i}^T Q_{i+1}
 // (RBL_gpu.jl:87) formed while Q_{i+1} is written.
+// ZX (MODE 0 with GRAM and XG, the 3-term update U' = U - Q_i A_i): Z is X itself, so Z^T Y' =
+// Q_i^T U' comes from the X rows already loaded — they pass through a per-wave LDS tile from the
+// 4x4x4 A layout into the 16x16x4 one, no second read of X.  CholQR turns it into the next step's
+// local-reorth coefficient Q_i^T Q_{i+1} = (Q_i^T U') R1^-1 R2^-1 (tsqr in rbl_api.cpp).
 //
 // Persistent grid: each wave walks 16-row tiles grid-stride (register budget), with the next
 // block's X (A layout, 16 B per lane) and Y (row-major, 16 B per lane) prefetched.  Y enters
@@ -51,6 +55,11 @@ constexpr int kRowThreads = 256;  // 4 waves
 #endif
 #ifndef RBL_RG_WPE_M1  // MODE 1 (CholQR2's Gram-only pass)
 #define RBL_RG_WPE_M1 RBL_RG_WPE_G
+#endif
+// the 3-term form's Z = X from the loaded rows (1) or loaded again, an L2 hit, which spills 14
+// VGPRs (0: for A/B runs)
+#ifndef RBL_ROWOP_ZX
+#define RBL_ROWOP_ZX 1
 #endif
 constexpr int kBlockRows = 16;    // rows per wave per iteration (one MFMA row tile)
 
@@ -112,9 +121,12 @@ __global__ __launch_bounds__(kRowThreads) __attribute__((amdgpu_waves_per_eu(MOD
   constexpr int kYPer = 16 * B / 128;       // row-major d2v per lane per 16-row tile
   constexpr int NG = CG * (CG + 1) / 2;     // Gram accumulators (upper triangle of quads)
   constexpr int NT = B / 16;                // 16-column tiles of the cross Gram
-  // LDS: alpha C | C2 (MODE 2) | the waves' output stages; the end-of-kernel Gram reductions
-  // reuse all of it
-  constexpr int kMain = B * LDC + (TWO ? B * LDC : 0) + 4 * 16 * B;
+  constexpr bool ZX = RBL_ROWOP_ZX && XG && GRAM && MODE == 0;  // Z is X: taken from the loaded rows
+  constexpr bool ZL = XG && !ZX;                // Z loaded from memory
+  constexpr int LDX = B + 2;                // X stage rows (ZX): 16 rows land 4 banks apart
+  // LDS: alpha C | C2 (MODE 2) | the waves' output stages | the waves' X stages (ZX); the
+  // end-of-kernel Gram reductions reuse all of it
+  constexpr int kMain = B * LDC + (TWO ? B * LDC : 0) + 4 * 16 * B + (ZX ? 4 * 16 * LDX : 0);
   constexpr int kRed = GRAM || XG ? 4 * B * B : 0;
   __shared__ __attribute__((aligned(16))) double lds[kMain > kRed ? kMain : kRed];
   double* cs = lds;
@@ -132,6 +144,7 @@ __global__ __launch_bounds__(kRowThreads) __attribute__((amdgpu_waves_per_eu(MOD
   __syncthreads();
 
   double* ot = lds + B * LDC + (TWO ? B * LDC : 0) + wave * 16 * B;
+  double* xs = lds + B * LDC + (TWO ? B * LDC : 0) + 4 * 16 * B + wave * 16 * LDX;
   auto swz = [](int row, int c) { return row * B + (c ^ (4 * ((row >> 2) & 3))); };
 
   const int64_t nblk = (nrows + kBlockRows - 1) / kBlockRows;
@@ -187,25 +200,30 @@ __global__ __launch_bounds__(kRowThreads) __attribute__((amdgpu_waves_per_eu(MOD
     for (int jt = 0; jt < (XG ? NT : 1); ++jt) gx[it][jt] = d4v{0.0, 0.0, 0.0, 0.0};
 
   d2v xa[1][NH], ya[1][kYPer];
-  double za[XG ? 4 : 1][XG ? NT : 1];
+  double za[ZL ? 4 : 1][ZL ? NT : 1];
   const bool by = MODE == 0 && beta != 0.0;  // the CholQR forms have beta = 0: no Y registers
   const int64_t blk_c = blk < nblk ? blk : nblk - 1;
   load_x(blk_c, xa);
   if (by) load_y(blk_c, ya);
-  if constexpr (XG) load_z(blk_c, za);
+  if constexpr (ZL) load_z(blk_c, za);
   for (; blk < nblk; blk += stride) {
     // keep the C operands in LDS: without this compiler barrier LLVM hoists their reads out
     // of the loop and holds 32 x 16 B per lane in registers (occupancy 1, spills)
     asm volatile("" ::: "memory");
     d2v xn[1][NH], yn[1][kYPer];
-    double zn[XG ? 4 : 1][XG ? NT : 1];
+    double zn[ZL ? 4 : 1][ZL ? NT : 1];
     {
       const int64_t bn = blk + stride < nblk ? blk + stride : nblk - 1;  // clamped prefetch
       load_x(bn, xn);
       if (by) load_y(bn, yn);
-      if constexpr (XG) load_z(bn, zn);
+      if constexpr (ZL) load_z(bn, zn);
     }
     double acc[1][CG];
+    if constexpr (ZX) {  // the X rows into the wave's X stage (read back as Z below)
+#pragma unroll
+      for (int h = 0; h < NH; ++h)
+        *reinterpret_cast<d2v*>(xs + (lane & 15) * LDX + 8 * h + 2 * q) = xa[0][h];
+    }
 #pragma unroll
     for (int rt = 0; rt < 1; ++rt) {
       if (by) {  // beta Y into the D layout through the wave's LDS tile
@@ -275,8 +293,12 @@ __global__ __launch_bounds__(kRowThreads) __attribute__((amdgpu_waves_per_eu(MOD
           for (int jt = 0; jt < NT; ++jt) {
             const double yb = ot[swz(4 * s4 + q, 16 * jt + (lane & 15))];
 #pragma unroll
-            for (int it = 0; it < NT; ++it)
-              gx[it][jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(lz ? za[s4][it] : 0.0, yb, gx[it][jt], 0, 0, 0);
+            for (int it = 0; it < NT; ++it) {
+              double zv;
+              if constexpr (ZX) zv = xs[(4 * s4 + q) * LDX + 16 * it + (lane & 15)];
+              else zv = za[s4][it];
+              gx[it][jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(lz ? zv : 0.0, yb, gx[it][jt], 0, 0, 0);
+            }
           }
         }
       }
@@ -298,7 +320,7 @@ __global__ __launch_bounds__(kRowThreads) __attribute__((amdgpu_waves_per_eu(MOD
 #pragma unroll
       for (int m = 0; m < kYPer; ++m) ya[rt][m] = yn[rt][m];
     }
-    if constexpr (XG) {
+    if constexpr (ZL) {
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4)
 #pragma unroll
@@ -401,6 +423,11 @@ bool launch_rowgram(const RowOpArgs& a, int64_t nrows, int grid, hipStream_t s) 
     return true;
   }
   if (a.X32) return false;
+  if (a.mode == 0 && xg && gram) {  // the 3-term update with U'^T U' and Q_i^T U' (Z is X)
+    if (a.Z != a.X || a.Y32) return false;
+    launch_rg<B, true, false, false, 0, true>(a, nrows, grid, s);
+    return true;
+  }
   if (a.mode == 0 && xg && !gram) {  // CholQR pass 3 with the next step's local-reorth Gram
     if (a.Y32) launch_rg<B, false, false, true, 0, true>(a, nrows, grid, s);
     else launch_rg<B, false, false, false, 0, true>(a, nrows, grid, s);

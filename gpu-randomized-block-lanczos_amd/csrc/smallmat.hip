@@ -614,6 +614,104 @@ void cloc_rinv(double* C, const double* Rinv, int b, const int* skip, hipStream_
   hipLaunchKernelGGL(k_cloc_rinv, dim3(1), dim3(256), 0, s, C, Rinv, b, skip);
 }
 
+// C = (C R1^-1) R2^-1 (b x b row-major, both factors upper triangular): the 3-term pass's
+// M = Q_i^T U' becomes Q_i^T Q_{i+1} through CholQR2's two factors, Q_{i+1} = U' R1^-1 R2^-1
+__global__ void k_cloc_rinv2(double* __restrict__ C, const double* __restrict__ R1inv,
+                             const double* __restrict__ R2inv, int b) {
+  __shared__ double c[32 * 32], d[32 * 32], f[32 * 32];  // b <= 32 (rowgram_ok); all in LDS
+  const int bb = b * b;
+  for (int e = threadIdx.x; e < bb; e += blockDim.x) {
+    c[e] = C[e];
+    f[e] = R1inv[e];
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < bb; e += blockDim.x) {
+    const int r = e / b, col = e % b;
+    double acc = 0.0;
+    for (int k = 0; k <= col; ++k) acc += c[r * b + k] * f[k * b + col];
+    d[e] = acc;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < bb; e += blockDim.x) f[e] = R2inv[e];
+  __syncthreads();
+  for (int e = threadIdx.x; e < bb; e += blockDim.x) {
+    const int r = e / b, col = e % b;
+    double acc = 0.0;
+    for (int k = 0; k <= col; ++k) acc += d[r * b + k] * f[k * b + col];
+    C[e] = acc;
+  }
+}
+void cloc_rinv2(double* C, const double* R1inv, const double* R2inv, int b, hipStream_t s) {
+  hipLaunchKernelGGL(k_cloc_rinv2, dim3(1), dim3(1024), 0, s, C, R1inv, R2inv, b);
+}
+
+// May Q^T Q' = (Q^T U) R^-1 stand in for the Gram of Q' = U R^-1 itself?  Both the rounding of
+// M = Q^T U (|dM[r][j]| <~ eps |u_j|) and that of the apply U R^-1 reach the coefficient scaled
+// by E = max_c sum_j |u_j| |R^-1[j][c]|, |u_j| = |R[:, j]| the column norms of U — an error of
+// eps E against the few eps of the direct Gram (E >= 1; E ~ cond(U) when U is graded).
+// gate[0] = 1 (derived) iff the first Cholesky was not shifted and E <= tau, gate[1] = !gate[0]
+// (direct).  R, Rinv: the first pass's factor and its inverse, equal on every rank; b <= 32.
+__global__ void k_cloc_gate(const double* __restrict__ R, const double* __restrict__ Rinv, int b,
+                            const int* __restrict__ need3, double tau, int* __restrict__ gate) {
+  __shared__ double rs[32 * 32], ri[32 * 32], d[256], e[256];
+  for (int x = threadIdx.x; x < b * b; x += blockDim.x) {
+    rs[x] = R[x];
+    ri[x] = Rinv[x];
+  }
+  __syncthreads();
+  const int c = threadIdx.x;
+  double s = 0.0;
+  if (c < b)
+    for (int k = 0; k <= c; ++k) s += rs[k * b + c] * rs[k * b + c];
+  d[c] = sqrt(s);
+  __syncthreads();
+  double t = 0.0;
+  if (c < b)
+    for (int j = 0; j <= c; ++j) t += d[j] * fabs(ri[j * b + c]);
+  e[c] = t;
+  __syncthreads();
+  if (c == 0) {
+    bool ok = need3[0] == 0;
+    for (int j = 0; j < b; ++j) ok = ok && e[j] <= tau;  // a NaN fails the comparison
+    gate[0] = ok;
+    gate[1] = !ok;
+  }
+}
+void cloc_gate(const double* R, const double* Rinv, int b, const int* need3, double tau, int* gate,
+               hipStream_t s) {
+  hipLaunchKernelGGL(k_cloc_gate, dim3(1), dim3(256), 0, s, R, Rinv, b, need3, tau, gate);
+}
+
+// G -= Cm^T Ci for the block-CGS coefficients D = W^T [Q_i | Q_{i-1}] = [Ci | Cm] (K x 2b
+// row-major, K = nW b): the local-reorth coefficient after the partial reorth,
+// Q'_{i-1}^T Q'_i = G - Cm^T Ci (+ Cm^T (W^T W - I) Ci, dropped), from G = Q_{i-1}^T Q_i before it.
+// Workgroup r forms row r; the k range is cut into blockDim / b contiguous chunks, each summed
+// in ascending k by one thread per column, and the chunk sums are added in chunk order: a fixed
+// summation order, no atomics.
+constexpr int kClocSubThreads = 1024;
+__global__ __launch_bounds__(kClocSubThreads) void k_cloc_sub(double* __restrict__ G,
+                                                              const double* __restrict__ D, int K, int b) {
+  __shared__ double part[kClocSubThreads];
+  const int r = blockIdx.x, ng = kClocSubThreads / b;
+  const int kg = threadIdx.x / b, c = threadIdx.x % b;
+  const int chunk = (K + ng - 1) / ng;
+  double acc = 0.0;
+  if (kg < ng) {
+    const int k1 = min(K, (kg + 1) * chunk);
+    for (int k = kg * chunk; k < k1; ++k) acc += D[(int64_t)k * 2 * b + b + r] * D[(int64_t)k * 2 * b + c];
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  if (kg == 0) {
+    double sum = part[c];
+    for (int g = 1; g < ng; ++g) sum += part[g * b + c];
+    G[r * b + c] -= sum;
+  }
+}
+void cloc_sub(double* G, const double* D, int nW, int b, hipStream_t s) {
+  hipLaunchKernelGGL(k_cloc_sub, dim3(b), dim3(kClocSubThreads), 0, s, G, D, nW * b, b);
+}
+
 // dst = src^T (b x b row-major): B_i^T for the dense path's 3-term epilogue
 __global__ void k_transpose_small(const double* __restrict__ src, double* __restrict__ dst, int b) {
   for (int e = threadIdx.x; e < b * b; e += blockDim.x) dst[(e % b) * b + e / b] = src[e];

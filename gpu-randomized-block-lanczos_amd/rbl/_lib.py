@@ -36,6 +36,7 @@ RBL_OPT_FUSE = 6
 RBL_OPT_HALO_OVERLAP = 7
 RBL_OPT_RELABEL = 8
 RBL_OPT_HALO_PUSH = 9
+RBL_OPT_CLOC_DERIVE = 10
 # rbl_path_stats entries
 RBL_PATH_SPMM = 0
 RBL_PATH_SPMM_LOC_FUSED = 1
@@ -45,7 +46,9 @@ RBL_PATH_LOCFIX_EDGES = 4
 RBL_PATH_LOCFIX_REST = 5
 RBL_PATH_SPMM_TWO_WAVE = 6
 RBL_PATH_RITZ_PIECES = 7
-RBL_PATH_NSTATS = 8
+RBL_PATH_CLOC_3TERM = 8
+RBL_PATH_CLOC_REORTH = 9
+RBL_PATH_NSTATS = 10
 RBL_BUILD_VARIANTS = 1
 # a rectangular B (rbl_set_matrix_normal): what rbl_spmm_kernel_for / rbl_matrix_format report
 RBL_SPMM_KERNEL_RECT = 8

@@ -768,13 +768,16 @@ class Context:
         """Which code path the steps took since the last reset (rbl_path_stats), counted as the
         work is issued: SpMM launches, those that applied the local-reorth update, separate
         local-reorth passes and Grams, the fused path's edge fix-ups, two-wave SpMM launches
-        (variants build only), and rbl_ritz calls that took the row-piece form."""
+        (variants build only), rbl_ritz calls that took the row-piece form, and local-reorth
+        coefficients taken from the 3-term pass or derived through the partial reorth
+        (RBL_OPT_CLOC_DERIVE)."""
         from . import _lib as L
         out = np.zeros(L.RBL_PATH_NSTATS, np.int64)
         self._check(lib.rbl_path_stats(self._h, i64ptr(out), L.RBL_PATH_NSTATS, int(reset)),
                     "rbl_path_stats")
         return dict(zip(("spmm", "spmm_loc_fused", "loc_separate", "loc_gram", "locfix_edges",
-                         "locfix_rest", "spmm_two_wave", "ritz_pieces"), (int(x) for x in out)))
+                         "locfix_rest", "spmm_two_wave", "ritz_pieces", "cloc_3term",
+                         "cloc_reorth"), (int(x) for x in out)))
 
     def allgather(self, values) -> np.ndarray:
         """rbl_allgather_host: every rank's int64 values, shape (nranks, len(values)); ordered

@@ -138,6 +138,25 @@ extern "C" {
                                    * referenced row (< 0.85x); 1 always; 0 never.  Results differ
                                    * from the pull-all halo only in the order of each row's sum. */
 
+#define RBL_OPT_CLOC_DERIVE   10  /* 1 (default): the local-reorth coefficient Q_{i-1}^T Q_i is
+                                   * derived from sums the step forms anyway instead of a Gram
+                                   * of its own.  The 3-term pass U' = U - Q_i A_i also forms
+                                   * M = Q_i^T U' from the rows it holds, and CholQR's factors
+                                   * give Q_i^T Q_{i+1} = M R1^-1 R2^-1 (R3^-1), so the QR's last
+                                   * pass no longer reads Q_i.  On a step with a block-CGS partial
+                                   * reorth (b = 32) the coefficient after it is G - Cm^T Ci with
+                                   * G the one before it and [Ci | Cm] = W^T [Q_i | Q_{i-1}], the
+                                   * reorth's own coefficients; the term Cm^T (W^T W - I) Ci is
+                                   * dropped.  Where U' is graded (decided on the device from
+                                   * R1: the derived value's error grows with cond(U')) or the
+                                   * Cholesky was shifted, the QR's last pass forms the Gram as
+                                   * before.  Same results to rounding (1e-12).  Needs the fp64
+                                   * basis, b in {16, 32}, RBL_OPT_FUSE bits 0 and 1,
+                                   * RBL_OPT_REORTH_ORDER 0 and a basis held whole in HBM (on
+                                   * several ranks: RBL_OPT_DEVICE_BLOCKS 0); not used on
+                                   * filtered steps or the arrow step after a thick restart.
+                                   * 0, or any of these unmet: the routes of RBL_OPT_FUSE bit 1. */
+
 typedef struct rbl_ctx rbl_ctx;
 
 int rbl_abi_version(void);
@@ -752,7 +771,11 @@ int rbl_allgather_host(rbl_ctx* ctx, const int64_t* mine, int64_t* all, int n);
                                        (variants build only; 0 in the product library)        */
 #define RBL_PATH_RITZ_PIECES     7  /* rbl_ritz calls that formed V in row pieces on the side
                                        stream with the staged D2H behind them                  */
-#define RBL_PATH_NSTATS          8
+#define RBL_PATH_CLOC_3TERM      8  /* local-reorth coefficients taken from the 3-term pass
+                                       (RBL_OPT_CLOC_DERIVE: M R1^-1 R2^-1)                    */
+#define RBL_PATH_CLOC_REORTH     9  /* local-reorth coefficients derived through the partial
+                                       reorth (RBL_OPT_CLOC_DERIVE: G - Cm^T Ci)               */
+#define RBL_PATH_NSTATS          10
 int rbl_path_stats(rbl_ctx* ctx, int64_t* out, int nstats, int reset);
 
 /* ---- host-only planning (callable without a GPU) -------------------------------------- */
