@@ -524,6 +524,12 @@ int tsmm44_xg_grid(int64_t nrows);
 void tsmm44(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
             double alpha, double beta, const int* skip, hipStream_t s, double* xslab = nullptr,
             int* xgrid = nullptr);
+// [Y0 | Y1] -= X C with the products rounded to fp32 and summed on fp32 MFMA (k_tsmm44x32): X fp64
+// panels of 32, Y two fp64 panels of 32, C fp64 row-major; for coefficients C of rounding size
+// only (upd32_gate).  tsmm44x32_ok: the shapes it takes (nrows >= 32, no aliasing).
+bool tsmm44x32_ok(int64_t nrows, const PanelRun& X, const Panels& Y);
+void tsmm44x32(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
+               const int* skip, hipStream_t s);
 
 // --- reorth32.hip: the fp32 Krylov basis (mixed precision, b in {16, 32}) ---------------
 // Gram partials slab[s][a][c] = sum over split s of W[r][a] X[r][c] (W: nW fp32 panels of
@@ -561,6 +567,13 @@ void cloc_rinv2(double* C, const double* R1inv, const double* R2inv, int b, hipS
 // max_c sum_j |R[:, j]| |Rinv[j][c]| <= tau; gate[1] = !gate[0].  b <= 32 (k_cloc_gate)
 void cloc_gate(const double* R, const double* Rinv, int b, const int* need3, double tau, int* gate,
                hipStream_t s);
+// May the update Y -= W C run with W C formed in fp32 (tsmm44x32)?  C: K x ncols row-major, equal
+// on every rank (all-reduced).  g = max_c |C_c|_2 sqrt(K) 2^-24 / eps is the fp32 rounding of a
+// column of W C in units of the fp64 rounding of Y; taken iff g <= tau or force (a NaN refuses).
+// flags = [skip of the fp32 kernel, skip of the fp64 kernel, taken count, refused count];
+// *g_out = g (diagnostics).  ncols <= 64 (k_upd32_gate)
+void upd32_gate(const double* C, int K, int ncols, double tau, int force, int* flags, double* g_out,
+                hipStream_t s);
 // G -= Cm^T Ci with D = [Ci | Cm] (nW b x 2b row-major), b <= 256; a fixed summation order
 // (k_cloc_sub)
 void cloc_sub(double* G, const double* D, int nW, int b, hipStream_t s);

@@ -251,6 +251,9 @@ struct RunBufs {
 // ---- buffers that live as long as the context (rbl_free)
 struct CtxBufs {
   PinBuf<char> h_d2h[2];  // pinned slots of the staged D2H (d2h_staged)
+  // RBL_OPT_UPD32 (k_upd32_gate); the counts are rbl_path_stats entries, so they outlive a run
+  DevBuf<int> d_upd32;       // [skip fp32 kernel, skip fp64 kernel, taken, refused]
+  DevBuf<double> d_upd32_g;  // the gate's value g of step i at [i % kUpd32Log] (diagnostics)
 };
 
 }  // namespace rbl::api
@@ -398,6 +401,9 @@ struct rbl_ctx : rbl::api::MatrixBufs, rbl::api::RunBufs, rbl::api::CtxBufs {
   // through a block-CGS partial reorth as G - Cm^T Ci (cloc_derive_on)
   bool cloc_derive = true;
   int cloc_src = 0;           // who formed S_CLOC: 0 a Gram pass, 1 the 3-term pass, 2 G - Cm^T Ci
+  // RBL_OPT_UPD32: the partial-reorth update W C on fp32 MFMA where its coefficients are rounding
+  // residue (0 off, 1 decided per step on the device by upd32_gate, 2 always: tests and probes)
+  int upd32 = 1;
   bool plan_all_resident = false;  // this run was started with RBL_OPT_DEVICE_BLOCKS = 0
   std::vector<int> step_flags;  // part_reorth flags per step (the fusion's schedule guess)
   double stage_ms[RBL_NUM_STAGES] = {0};
@@ -1950,6 +1956,13 @@ int filter_apply(rbl_ctx* ctx, const double* X, int b, double* out, const DevBuf
   return cheb_apply(ctx, X, b, out, F[0], F[1]);
 }
 
+// RBL_OPT_UPD32: the fp32 route is taken for g <= tau (k_upd32_gate).  At 1/2 the fp32 route's
+// column error is 1.1 .. 1.3x the fp64 route's (tests/test_upd32_host.py holds it to 8x, which a
+// NumPy restatement reaches near g = 4); a C4a run sits at g = 0.16 on step 4 and <= 0.08 after
+// (DESIGN §3), so nothing is gained above 1/2.
+constexpr double kUpd32Tau = 0.5;
+constexpr int kUpd32Log = 64;  // steps whose gate value is kept (rbl_upd32_gate_values)
+
 // X -= l (l^T X) for every locked vector l in lock order (restarted.jl:1-21,
 // restart_reorth_gpu!: one projection per locked vector, MGS over them).
 int lock_reorth(rbl_ctx* ctx, double* X) {
@@ -2018,7 +2031,28 @@ int reorth_pair(rbl_ctx* ctx, int i, int flags) {
       W.count = nres;
       W.w = b;
       CHK(gram(ctx, W, pan2(Qi, Qm, b), ctx->d_C, nullptr));
-      CHK(update(W, nres == nW));
+      // RBL_OPT_UPD32: where the update runs plain (b = 32, all of W resident, no locked vectors on
+      // this step, no cross-Gram epilogue: the derive branch, or RBL_OPT_FUSE without bit 1) and
+      // d_C is rounding residue, W C is formed on fp32 MFMA.  Both kernels are enqueued and the
+      // gate's flags let one run: the gate reads all-reduced values only, so every rank takes the
+      // same route, and the routes differ in no collective.  The guards are options and plan
+      // state, as cloc_derive_on's.
+      const Panels Yp = pan2(Qi, Qm, b);
+      // (a rank without rows, or with too few for the fp32 kernel, still counts the step)
+      const bool gate32 = ctx->upd32 != 0 && b == 32 && !xg && nres == nW && !((flags & 2) && ctx->nlock > 0);
+      const bool u32 = gate32 && ctx->nloc > 0 && tsmm44x32_ok(ctx->nloc, W, Yp);
+      if (gate32) {
+        upd32_gate(ctx->d_C, nW * b, 2 * b, kUpd32Tau, ctx->upd32 == 2, ctx->d_upd32,
+                   ctx->d_upd32_g + (i % kUpd32Log), ctx->stream);
+        HIPC(hipGetLastError());
+      }
+      if (u32) {
+        tsmm44x32(ctx->nloc, W, ctx->d_C, 2 * b, Yp, ctx->d_upd32, ctx->stream);
+        HIPC(hipGetLastError());
+        CHK(tsmm_checked(ctx, W, ctx->d_C, 2 * b, Yp, -1.0, 1.0, ctx->d_upd32 + 1));
+      } else {  // (also a rank whose rows do not fit the fp32 kernel: fp64 whatever the gate says)
+        CHK(update(W, nres == nW));
+      }
     } else {  // ascending-j block MGS, exactly the reference order
       for (int j = 0; j < nres; ++j) {
         const PanelRun W = run1(slotp(ctx, j), b);
@@ -3019,6 +3053,10 @@ int rbl_set_option(rbl_ctx* ctx, int option, int64_t value) {
       if (value < 0 || value > 1) return fail(ctx, RBL_ERR_INVALID, "RBL_OPT_CLOC_DERIVE must be 0|1");
       ctx->cloc_derive = value != 0;
       return RBL_OK;
+    case RBL_OPT_UPD32:
+      if (value < 0 || value > 2) return fail(ctx, RBL_ERR_INVALID, "RBL_OPT_UPD32 must be 0|1|2");
+      ctx->upd32 = (int)value;
+      return RBL_OK;
     default: return fail(ctx, RBL_ERR_INVALID, "unknown option");
   }
 }
@@ -3972,6 +4010,12 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   HIPC(hipMemset(ctx->d_small, 0, (size_t)S_NSMALL * b * b * sizeof(double)));  // (S_CX is summed before it is first written)
   HIPC(ctx->d_flags.alloc(6));
   HIPC(hipMemset(ctx->d_flags, 0, 6 * sizeof(int)));
+  if (!ctx->d_upd32) {  // kept across runs: its counters are rbl_path_stats entries
+    HIPC(ctx->d_upd32.alloc(4));
+    HIPC(hipMemset(ctx->d_upd32, 0, 4 * sizeof(int)));
+    HIPC(ctx->d_upd32_g.alloc(kUpd32Log));
+    HIPC(hipMemset(ctx->d_upd32_g, 0, kUpd32Log * sizeof(double)));
+  }
   {
 #ifdef RBL_VARIANTS
     const char* e = std::getenv("RBL_STASH_COPY");  // A/B: 1 = device record + D2H copy
@@ -5856,9 +5900,29 @@ int rbl_comm_stats(rbl_ctx* ctx, int64_t* out, int nstats, int reset) {
 
 int rbl_path_stats(rbl_ctx* ctx, int64_t* out, int nstats, int reset) {
   if (!ctx || nstats < 0 || (nstats > 0 && !out)) return RBL_ERR_INVALID;
+  // the fp32-update gate counts on the device (k_upd32_gate): read back behind the stream
+  if (ctx->d_upd32) {
+    int cnt[2] = {0, 0};
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    HIPC(hipMemcpy(cnt, ctx->d_upd32 + 2, sizeof(cnt), hipMemcpyDeviceToHost));
+    ctx->path_stats[RBL_PATH_UPD32_TAKEN] = cnt[0];
+    ctx->path_stats[RBL_PATH_UPD32_REFUSED] = cnt[1];
+    if (reset) HIPC(hipMemset(ctx->d_upd32 + 2, 0, sizeof(cnt)));
+  }
   for (int i = 0; i < nstats; ++i) out[i] = i < RBL_PATH_NSTATS ? ctx->path_stats[i] : 0;
   if (reset)
     for (int64_t& v : ctx->path_stats) v = 0;
+  return RBL_OK;
+}
+
+int rbl_upd32_gate_values(rbl_ctx* ctx, double* out, int n) {
+  if (!ctx || n < 0 || (n > 0 && !out)) return RBL_ERR_INVALID;
+  for (int i = 0; i < n; ++i) out[i] = 0.0;
+  if (!ctx->d_upd32_g || n == 0) return RBL_OK;
+  HIPC(hipSetDevice(ctx->device));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  HIPC(hipMemcpy(out, ctx->d_upd32_g, (size_t)std::min(n, kUpd32Log) * sizeof(double), hipMemcpyDeviceToHost));
   return RBL_OK;
 }
 

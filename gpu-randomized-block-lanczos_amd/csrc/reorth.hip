@@ -8,6 +8,8 @@
 //   * k_tsmm44:  Y = beta Y + alpha X C  with X a run of panels — the partial-reorth update
 //                (RBL_gpu.jl:34,40), the 3-term / local-reorth updates, CholQR apply and the
 //                Ritz projection V = [Q_1..Q_m] S (RBL_gpu.jl:121, RBL.jl:68).
+// And one fp32-MFMA kernel over the same fp64 data, k_tsmm44x32: the partial-reorth update where
+// its coefficients are rounding residue (RBL_OPT_UPD32).
 //
 // v_mfma_f64_4x4x4f64 lane layout (tools/mfma_layout_probe.hip), block g = (lane>>2)&3:
 //   A[i = lane&3][k = lane>>4], B[k = lane>>4][j = lane&3], D[i = lane>>4][j = lane&3].
@@ -948,6 +950,152 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kT44fNrt ==
   }
   };
   tile_body(blockIdx.x);
+}
+
+// ----------------------------------------------------------------------------------------
+// [Y0 | Y1] -= W C with the products on fp32 MFMA (v_mfma_f32_16x16x4_f32): the partial-reorth
+// update when its coefficients are rounding residue (k_upd32_gate decides).  W (fp64,
+// panels of 32) and Y (fp64, two panels of 32) stay in HBM as they are; W is rounded to fp32 in
+// registers after the load, C is staged in LDS as (float)C, the 32 x 64 product of a wave is
+// summed in fp32 and subtracted from Y in fp64.  With |C| ~ eps the fp32 rounding of W C,
+// 2^-24 sqrt(K) |W| |C|, stays below the fp64 rounding of Y - W C itself.
+// Shape limits of k_tsmm44f: K a multiple of 32, nrows >= 32, a wave past nrows computes the last
+// 32 rows and stores only its own.  The basis loads are k_tsmm44f's: rows rw + 16 rt + (lane & 15),
+// k = 32 ch + 8 h + 2 q + v as one 16-B load per (rt, h) — 64 contiguous bytes per row and
+// instruction, a wave-uniform base plus a lane constant.  MFMA step (h, v) takes k = 8 h + 2 q + v
+// in lane group q for A and B alike; B[k][16 ct + c16] sits at cs[k][4 c16 + ct] (one
+// ds_read_b128 feeds the four column tiles of both row tiles).
+// ----------------------------------------------------------------------------------------
+typedef float f2v32 __attribute__((ext_vector_type(2)));
+typedef float f4v32 __attribute__((ext_vector_type(4)));
+constexpr int kU32Rows = 32;  // rows per wave (k_tsmm44x32)
+__global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
+                                                   const double* __restrict__ C, int ldc, double* Y0,
+                                                   double* Y1, const int* skip) {
+  if (skip && *skip) return;
+  constexpr int W = 32, KYP = 64, CT = 4, CLD = 64, KF = 32, NH = KF / 8, OLD = KYP + 4;
+  // two C buffers; after the k-loop the same LDS holds the 4 waves' 16 x (64 + 4) fp32 tiles
+  __shared__ __attribute__((aligned(16))) float cs[2][KF * CLD + 128];
+  static_assert(2 * (KF * CLD + 128) >= 4 * 16 * OLD, "epilogue tiles fit");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int q = lane >> 4, c16 = lane & 15;
+  const int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * kU32Rows;
+  const int64_t rw = r0 + kU32Rows <= nrows ? r0 : nrows - kU32Rows;  // wave-uniform
+  const int nch = X.count;  // one 32-column basis panel per chunk
+
+  f4v32 acc[2][CT];
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+    for (int c = 0; c < CT; ++c) acc[rt][c] = f4v32{0.f, 0.f, 0.f, 0.f};
+
+  const unsigned aoff0 = (unsigned)(c16 * W + 2 * q);
+  auto load_a = [&](int ch, d2v (&ar)[2][NH]) {
+    const int chc = ch < nch ? ch : nch - 1;
+    const double* xb = X.base + (int64_t)chc * X.stride + rw * W;  // uniform
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt)
+        ar[rt][h] = *reinterpret_cast<const d2v*>(xb + (aoff0 + (unsigned)(16 * rt * W + 8 * h)));
+  };
+  auto round_a = [&](const d2v (&ar)[2][NH], float (&af)[2][NH][2]) {
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int h = 0; h < NH; ++h) {
+        af[rt][h][0] = (float)ar[rt][h].x;
+        af[rt][h][1] = (float)ar[rt][h].y;
+      }
+  };
+  // C chunk 32 x 64: thread (k = tid / 16 + 16 hh, cc = tid % 16) moves C[k][cc + 16 ct]
+  const int ck = tid >> 4, ccc = tid & 15;
+  auto load_c = [&](int ch, float (&cr)[2][CT]) {
+    const int chc = ch < nch ? ch : nch - 1;
+    const double* cb = C + (int64_t)(KF * chc + ck) * ldc + ccc;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) cr[hh][ct] = (float)cb[(int64_t)(16 * hh) * ldc + 16 * ct];
+  };
+  auto store_c = [&](int buf, const float (&cr)[2][CT]) {
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+      *reinterpret_cast<f4v32*>(&cs[buf][(ck + 16 * hh) * CLD + 4 * ccc]) =
+          f4v32{cr[hh][0], cr[hh][1], cr[hh][2], cr[hh][3]};
+  };
+
+  d2v anext[2][NH];
+  float af[2][NH][2];
+  float cr[2][CT];
+  load_c(0, cr);
+  store_c(0, cr);
+  load_a(0, anext);
+  round_a(anext, af);
+  __syncthreads();
+  for (int ch = 0; ch < nch; ++ch) {
+    load_c(ch + 1, cr);  // unconditional, clamped (see k_gram44)
+    load_a(ch + 1, anext);
+    const float* cb = cs[ch & 1] + 2 * q * CLD + 4 * c16;
+#pragma unroll
+    for (int hv = 0; hv < 2 * NH; ++hv) {
+      const int h = hv >> 1, v = hv & 1;
+      const f4v32 bv = *reinterpret_cast<const f4v32*>(cb + (8 * h + v) * CLD);
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int c = 0; c < CT; ++c)
+          acc[rt][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[rt][h][v], bv[c], acc[rt][c], 0, 0, 0);
+    }
+    store_c((ch + 1) & 1, cr);
+    round_a(anext, af);
+    __syncthreads();
+  }
+  // epilogue: D (lane: rows 4 q + v, column c16 of tile c) -> LDS (free after the loop's last
+  // barrier) -> Y read and written row-major, 16 B (two columns) per lane; rows below r0 are
+  // the previous wave's (shifted last tile)
+  float* ot = &cs[0][0] + wave * 16 * OLD;
+  const int ce = (2 * lane) % KYP, rl = (2 * lane) / KYP;
+  double* yb = (ce < W ? Y0 + ce : Y1 + (ce - W)) + (rw + rl) * W;
+  const int dskip = (int)(r0 - rw);
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt) {
+#pragma unroll
+    for (int c = 0; c < CT; ++c)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) ot[(4 * q + v) * OLD + 16 * c + c16] = acc[rt][c][v];
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const int row = rl + 2 * m;
+      const f2v32 p = *reinterpret_cast<const f2v32*>(ot + row * OLD + ce);
+      if (16 * rt + row >= dskip) {
+        d2v* yp = reinterpret_cast<d2v*>(yb + (int64_t)((16 * rt + 2 * m) * W));
+        d2v y = *yp;
+        y.x -= (double)p.x;
+        y.y -= (double)p.y;
+        *yp = y;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+bool tsmm44x32_ok(int64_t nrows, const PanelRun& X, const Panels& Y) {
+  if (X.w != 32 || X.count < 1 || !X.base || Y.count != 2 || Y.w != 32 || nrows < kU32Rows) return false;
+  for (int t = 0; t < Y.count; ++t)  // as tsmm44's fast path: Y must not alias the X panels
+    if (Y.ptr[t] >= X.base && Y.ptr[t] < X.base + (int64_t)X.count * X.stride) return false;
+  return true;
+}
+
+void tsmm44x32(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
+               const int* skip, hipStream_t st) {
+  const int64_t wgs = (nrows + 4 * kU32Rows - 1) / (4 * kU32Rows);
+  hipLaunchKernelGGL(k_tsmm44x32, dim3((unsigned)wgs), dim3(256), 0, st, nrows, X, C, ldc,
+                     const_cast<double*>(Y.ptr[0]), const_cast<double*>(Y.ptr[1]), skip);
 }
 
 // the epilogue stores Y row-major 16 B (two columns) per lane: Y panel widths must be even

@@ -682,6 +682,59 @@ void cloc_gate(const double* R, const double* Rinv, int b, const int* need3, dou
   hipLaunchKernelGGL(k_cloc_gate, dim3(1), dim3(256), 0, s, R, Rinv, b, need3, tau, gate);
 }
 
+// May W C be formed in fp32 for the update Y -= W C (k_tsmm44x32)?  With W orthonormal to
+// rounding and both factors rounded to fp32 and summed in fp32, the error of a column of W C is
+// about 2^-24 sqrt(K) |C_c|_2 against the eps |Y_c| ~ eps the fp64 subtraction commits anyway:
+// g = max_c |C_c|_2 sqrt(K) 2^-24 / eps, taken iff g <= tau (tau = 1/2: the fp32 route's column
+// error stays within 8x the fp64 route's, tests/test_upd32_host.py).  C is the all-reduced
+// coefficient, equal on every rank, so every rank decides alike.  Column sums of squares in a
+// fixed order (kUpd32GateThreads / 64 strided k groups, added in group order); a NaN refuses.
+constexpr int kUpd32GateThreads = 1024;
+__global__ __launch_bounds__(kUpd32GateThreads) void k_upd32_gate(const double* __restrict__ C, int K,
+                                                                  int ncols, double tau, int force,
+                                                                  int* __restrict__ flags,
+                                                                  double* __restrict__ g_out) {
+  __shared__ double part[kUpd32GateThreads];
+  __shared__ double ssq[64];
+  constexpr int NG = kUpd32GateThreads / 64;
+  const int c = threadIdx.x % 64, grp = threadIdx.x / 64;
+  double s = 0.0;
+  if (c < ncols)
+    for (int k = grp; k < K; k += NG) {
+      const double v = C[(int64_t)k * ncols + c];
+      s += v * v;
+    }
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (grp == 0) {
+    double t = part[c];
+    for (int g = 1; g < NG; ++g) t += part[64 * g + c];
+    ssq[c] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double m = 0.0;
+    bool finite = true;
+    for (int j = 0; j < ncols; ++j) {
+      finite = finite && ssq[j] == ssq[j];
+      m = ssq[j] > m ? ssq[j] : m;
+    }
+    // 2^-24 / eps = 2^28
+    const double g = finite ? sqrt(m) * sqrt((double)K) * 268435456.0 : __builtin_nan("");
+    const bool take = force || g <= tau;  // a NaN fails the comparison
+    flags[0] = !take;
+    flags[1] = take;
+    flags[2] += take;
+    flags[3] += !take;
+    if (g_out) *g_out = g;
+  }
+}
+void upd32_gate(const double* C, int K, int ncols, double tau, int force, int* flags, double* g_out,
+                hipStream_t s) {
+  hipLaunchKernelGGL(k_upd32_gate, dim3(1), dim3(kUpd32GateThreads), 0, s, C, K, ncols, tau, force, flags,
+                     g_out);
+}
+
 // G -= Cm^T Ci for the block-CGS coefficients D = W^T [Q_i | Q_{i-1}] = [Ci | Cm] (K x 2b
 // row-major, K = nW b): the local-reorth coefficient after the partial reorth,
 // Q'_{i-1}^T Q'_i = G - Cm^T Ci (+ Cm^T (W^T W - I) Ci, dropped), from G = Q_{i-1}^T Q_i before it.

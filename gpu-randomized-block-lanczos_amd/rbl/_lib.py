@@ -37,6 +37,7 @@ RBL_OPT_HALO_OVERLAP = 7
 RBL_OPT_RELABEL = 8
 RBL_OPT_HALO_PUSH = 9
 RBL_OPT_CLOC_DERIVE = 10
+RBL_OPT_UPD32 = 11
 # rbl_path_stats entries
 RBL_PATH_SPMM = 0
 RBL_PATH_SPMM_LOC_FUSED = 1
@@ -48,7 +49,9 @@ RBL_PATH_SPMM_TWO_WAVE = 6
 RBL_PATH_RITZ_PIECES = 7
 RBL_PATH_CLOC_3TERM = 8
 RBL_PATH_CLOC_REORTH = 9
-RBL_PATH_NSTATS = 10
+RBL_PATH_UPD32_TAKEN = 10
+RBL_PATH_UPD32_REFUSED = 11
+RBL_PATH_NSTATS = 12
 RBL_BUILD_VARIANTS = 1
 # a rectangular B (rbl_set_matrix_normal): what rbl_spmm_kernel_for / rbl_matrix_format report
 RBL_SPMM_KERNEL_RECT = 8
@@ -167,7 +170,8 @@ SIGNATURES = {
     "rbl_reset_timers": (C.c_int, [_p]),
     "rbl_comm_stats": (C.c_int, [_p, _pi64, C.c_int, C.c_int]),
     "rbl_path_stats": (C.c_int, [_p, _pi64, C.c_int, C.c_int]),
-    "rbl_allgather_host": (C.c_int, [_p, _pi64, _pi64, C.c_int]),
+    "rbl_upd32_gate_values": (C.c_int, [_p, _pd, C.c_int]),
+    "rbl_allgather_host":(C.c_int, [_p, _pi64, _pi64, C.c_int]),
     "rbl_synchronize": (C.c_int, [_p]),
     "rbl_plan_row_partition": (C.c_int, [_i64, _pi64, C.c_int, _pi64]),
     "rbl_plan_halo": (C.c_int, [_i64, _pi64, _pi64, C.c_int, C.c_int, _pi64, _pi64, _pi64]),

@@ -770,14 +770,23 @@ class Context:
         local-reorth passes and Grams, the fused path's edge fix-ups, two-wave SpMM launches
         (variants build only), rbl_ritz calls that took the row-piece form, and local-reorth
         coefficients taken from the 3-term pass or derived through the partial reorth
-        (RBL_OPT_CLOC_DERIVE)."""
+        (RBL_OPT_CLOC_DERIVE).  upd32_taken / upd32_refused: partial-reorth updates the device
+        gate sent to the fp32-MFMA kernel or kept on the fp64 one (RBL_OPT_UPD32), counted on the
+        device and read back after a stream synchronise."""
         from . import _lib as L
         out = np.zeros(L.RBL_PATH_NSTATS, np.int64)
         self._check(lib.rbl_path_stats(self._h, i64ptr(out), L.RBL_PATH_NSTATS, int(reset)),
                     "rbl_path_stats")
         return dict(zip(("spmm", "spmm_loc_fused", "loc_separate", "loc_gram", "locfix_edges",
                          "locfix_rest", "spmm_two_wave", "ritz_pieces", "cloc_3term",
-                         "cloc_reorth"), (int(x) for x in out)))
+                         "cloc_reorth", "upd32_taken", "upd32_refused"), (int(x) for x in out)))
+
+    def upd32_gate_values(self) -> np.ndarray:
+        """Diagnostics (rbl_upd32_gate_values): the RBL_OPT_UPD32 gate's g of block step i at
+        [i % 64], 0 where the gate has not run."""
+        out = np.zeros(64, np.float64)
+        self._check(lib.rbl_upd32_gate_values(self._h, dptr(out), 64), "rbl_upd32_gate_values")
+        return out
 
     def allgather(self, values) -> np.ndarray:
         """rbl_allgather_host: every rank's int64 values, shape (nranks, len(values)); ordered

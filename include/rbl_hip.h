@@ -157,6 +157,21 @@ extern "C" {
                                    * filtered steps or the arrow step after a thick restart.
                                    * 0, or any of these unmet: the routes of RBL_OPT_FUSE bit 1. */
 
+#define RBL_OPT_UPD32         11  /* the partial-reorth update [Q_i | Q_{i-1}] -= W C with W C
+                                   * formed on fp32 MFMA (W and C rounded to fp32, fp32 sums, the
+                                   * subtraction in fp64) where C = W^T [Q_i | Q_{i-1}] is rounding
+                                   * residue.  1 (default): decided per step on the device from the
+                                   * all-reduced C, g = max_c |C_c|_2 sqrt(K) 2^-24 / eps <= 1/2
+                                   * (the fp32 rounding of W C then stays below the fp64 rounding of
+                                   * the subtraction; every rank decides alike); otherwise the fp64
+                                   * update as before.  0: always fp64.  2: always fp32, for tests
+                                   * and probes only: it does NOT preserve results when C is not
+                                   * small.  Applies where the update runs plain: fp64 basis,
+                                   * b = 32, RBL_OPT_REORTH_ORDER 0, all of W in HBM, the
+                                   * RBL_OPT_CLOC_DERIVE route of that step, no locked vectors;
+                                   * everything else keeps the fp64 update.  Counted in
+                                   * rbl_path_stats (RBL_PATH_UPD32_TAKEN / _REFUSED). */
+
 typedef struct rbl_ctx rbl_ctx;
 
 int rbl_abi_version(void);
@@ -775,8 +790,15 @@ int rbl_allgather_host(rbl_ctx* ctx, const int64_t* mine, int64_t* all, int n);
                                        (RBL_OPT_CLOC_DERIVE: M R1^-1 R2^-1)                    */
 #define RBL_PATH_CLOC_REORTH     9  /* local-reorth coefficients derived through the partial
                                        reorth (RBL_OPT_CLOC_DERIVE: G - Cm^T Ci)               */
-#define RBL_PATH_NSTATS          10
+#define RBL_PATH_UPD32_TAKEN     10 /* partial-reorth updates the device gate sent to the fp32
+                                       kernel (RBL_OPT_UPD32) ...                              */
+#define RBL_PATH_UPD32_REFUSED   11 /* ... and those it kept on the fp64 kernel; both counted on
+                                       the device and read back behind the context's stream    */
+#define RBL_PATH_NSTATS          12
 int rbl_path_stats(rbl_ctx* ctx, int64_t* out, int nstats, int reset);
+/* Diagnostics: the value g of the RBL_OPT_UPD32 gate at block step i in out[i % 64] (n <= 64
+ * entries; 0 where the gate has not run).  Waits for the context's stream. */
+int rbl_upd32_gate_values(rbl_ctx* ctx, double* out, int n);
 
 /* ---- host-only planning (callable without a GPU) -------------------------------------- */
 /* nnz-balanced contiguous row partition: bounds_out[0..nranks] (bounds_out[0]=0). */

@@ -1,5 +1,6 @@
 // reorth_probe.cpp — time the shipped partial-reorth kernels (gram44_partial + reduce_slab,
-// tsmm44) at n = 1e7, b = 32, X = [Q_i, Q_{i-1}] for a range of basis sizes (diagnostic).
+// tsmm44, and at b = 32 the fp32-MFMA update tsmm44x32 of RBL_OPT_UPD32 beside it) at n = 1e7,
+// b = 32, X = [Q_i, Q_{i-1}] for a range of basis sizes (diagnostic).
 // Build: tools/build_probe.sh (links the library's objects).
 #include <hip/hip_runtime.h>
 
@@ -47,11 +48,12 @@ int main(int argc, char** argv) {
   double* xslab = nullptr;
   int xgrid = 0;
   if (hipMalloc(&xslab, (size_t)rbl::tsmm44_xg_grid(n) * 1024 * 8) != hipSuccess) return 1;
-  hipEvent_t e0, e1, e2;
+  hipEvent_t e0, e1, e2, e3;
   (void)hipEventCreate(&e0);
   (void)hipEventCreate(&e1);
   (void)hipEventCreate(&e2);
-  double tg = 0, tt = 0, fl = 0, byg = 0, byt = 0;
+  (void)hipEventCreate(&e3);
+  double tg = 0, tt = 0, tu = 0, fl = 0, byg = 0, byt = 0;
   for (int nW = 2; nW <= nWmax; nW += 2) {
     rbl::PanelRun Wr;
     Wr.base = W;
@@ -66,7 +68,8 @@ int main(int argc, char** argv) {
     X.count = 2;
     X.w = b;
     const int splits = rbl::gram44_splits(n, nW, b);
-    float bg = 1e30f, bt = 1e30f;
+    float bg = 1e30f, bt = 1e30f, bu = 1e30f;
+    const bool u32 = b == 32 && !xg && rbl::tsmm44x32_ok(n, Wr, X);
     for (int rep = 0; rep < 3; ++rep) {
       (void)hipEventRecord(e0);
       rbl::gram44_partial(n, Wr, X, slab, splits, nullptr, 0);
@@ -74,18 +77,25 @@ int main(int argc, char** argv) {
       (void)hipEventRecord(e1);
       rbl::tsmm44(n, Wr, C, xw, X, -1.0, 1.0, nullptr, 0, xg ? xslab : nullptr, &xgrid);
       (void)hipEventRecord(e2);
-      (void)hipEventSynchronize(e2);
-      float g, t;
+      if (u32) rbl::tsmm44x32(n, Wr, C, xw, X, nullptr, 0);  // the same update on fp32 MFMA
+      (void)hipEventRecord(e3);
+      (void)hipEventSynchronize(e3);
+      float g, t, u;
       (void)hipEventElapsedTime(&g, e0, e1);
       (void)hipEventElapsedTime(&t, e1, e2);
+      (void)hipEventElapsedTime(&u, e2, e3);
       if (rep) {
         bg = g < bg ? g : bg;
         bt = t < bt ? t : bt;
+        bu = u < bu ? u : bu;
       }
     }
     const double f = 2.0 * n * nW * b * xw;
-    printf("nW=%2d  splits %4d  gram %7.3f ms %5.1f TF   tsmm %7.3f ms %5.1f TF\n", nW, splits, bg, f / bg / 1e9, bt,
+    printf("nW=%2d  splits %4d  gram %7.3f ms %5.1f TF   tsmm %7.3f ms %5.1f TF", nW, splits, bg, f / bg / 1e9, bt,
            f / bt / 1e9);
+    if (u32) printf("   upd32 %7.3f ms %5.1f TF %5.2f TB/s", bu, f / bu / 1e9, 8.0 * n * (nW * b + 2 * xw) / bu / 1e9);
+    printf("\n");
+    if (u32) tu += bu;
     byg += 8.0 * n * (nW * b + xw);       // basis + X read once
     byt += 8.0 * n * (nW * b + 2 * xw);   // basis read, X read and written
     tg += bg;
@@ -94,5 +104,7 @@ int main(int argc, char** argv) {
   }
   printf("sum over nW=2..%d step 2: gram %.1f ms (%.1f TF, %.2f TB/s)  tsmm %.1f ms (%.1f TF, %.2f TB/s)\n", nWmax,
          tg, fl / tg / 1e9, byg / tg / 1e9, tt, fl / tt / 1e9, byt / tt / 1e9);
+  if (tu > 0)
+    printf("                        upd32 (fp32 MFMA) %.1f ms (%.1f TF, %.2f TB/s)\n", tu, fl / tu / 1e9, byt / tu / 1e9);
   return 0;
 }
