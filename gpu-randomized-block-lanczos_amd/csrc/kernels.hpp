@@ -530,6 +530,16 @@ void tsmm44(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Pa
 bool tsmm44x32_ok(int64_t nrows, const PanelRun& X, const Panels& Y);
 void tsmm44x32(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
                const int* skip, hipStream_t s);
+// The same update with an fp32 shadow of X (RBL_OPT_UPD32_SHADOW): S holds X.count slots of
+// tsmm44x32_shadow_slot(nrows) floats in the kernel's own layout; the leading nsh panels are read
+// from S, the others from X as above and their rounded values stored to S — also when *skip is set,
+// where no product is formed and Y stays.  Y has the bits of tsmm44x32.  cnt[0] += panels read from
+// S, cnt[1] += panels stored to it (device counters).  shadow_block_rowmajor: one slot (host copy)
+// as nrows x 32 row-major.
+int64_t tsmm44x32_shadow_slot(int64_t nrows);
+void tsmm44x32_shadow(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
+                      const int* skip, float* S, int nsh, int* cnt, hipStream_t s);
+void shadow_block_rowmajor(const float* slot, int64_t nrows, float* out);
 
 // --- reorth32.hip: the fp32 Krylov basis (mixed precision, b in {16, 32}) ---------------
 // Gram partials slab[s][a][c] = sum over split s of W[r][a] X[r][c] (W: nW fp32 panels of

@@ -49,6 +49,15 @@ int rbl_plan_halo(int64_t nrows_local, const int64_t* rowptr, const int64_t* col
   return RBL_OK;
 }
 
+// May the fp32 shadow of the basis (RBL_OPT_UPD32_SHADOW) be allocated?  Asked once the basis and
+// the run's other buffers are in place, with the device's free and total bytes as hipMemGetInfo
+// reports them then: yes when `needed` fits and a tenth of the device stays free after it, for what
+// a run allocates later (the Ritz vectors' V and W, filter blocks, locked vectors: a few slots).
+// The shadow is an accelerator only: the answer never changes the basis plan.
+int rbl_plan_shadow_fits(uint64_t free_bytes, uint64_t total_bytes, uint64_t needed_bytes) {
+  return needed_bytes <= free_bytes && free_bytes - needed_bytes >= total_bytes / 10;
+}
+
 int rbl_hashwindow_rows_host(int64_t n, int64_t halfwidth, double density, uint64_t seed,
                              int nplant, const double* plant, int64_t row_begin, int64_t row_end,
                              int64_t* rowptr_out, int64_t* colind_out, double* val_out) {

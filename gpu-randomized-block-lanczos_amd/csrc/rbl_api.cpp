@@ -246,13 +246,17 @@ struct RunBufs {
   // W = A V, (n_local + kRowPad) x ritz_kp row-major (ritz_kp = ritz_k rounded up to even)
   DevBuf<double> d_rv;
   DevBuf<double> d_rw;
+  // RBL_OPT_UPD32_SHADOW: (float) of basis blocks 0 .. max_blocks - 3 for the fp32 partial-reorth
+  // update, shadow_slot floats each in k_tsmm44x32's own layout; null: no shadow in this plan
+  DevBuf<float> d_shadow;
 };
 
 // ---- buffers that live as long as the context (rbl_free)
 struct CtxBufs {
   PinBuf<char> h_d2h[2];  // pinned slots of the staged D2H (d2h_staged)
   // RBL_OPT_UPD32 (k_upd32_gate); the counts are rbl_path_stats entries, so they outlive a run
-  DevBuf<int> d_upd32;       // [skip fp32 kernel, skip fp64 kernel, taken, refused]
+  DevBuf<int> d_upd32;       // [skip fp32 kernel, skip fp64 kernel, taken, refused, shadow panels
+                             //  read, panels rounded into the shadow]
   DevBuf<double> d_upd32_g;  // the gate's value g of step i at [i % kUpd32Log] (diagnostics)
 };
 
@@ -404,6 +408,13 @@ struct rbl_ctx : rbl::api::MatrixBufs, rbl::api::RunBufs, rbl::api::CtxBufs {
   // RBL_OPT_UPD32: the partial-reorth update W C on fp32 MFMA where its coefficients are rounding
   // residue (0 off, 1 decided per step on the device by upd32_gate, 2 always: tests and probes)
   int upd32 = 1;
+  // RBL_OPT_UPD32_SHADOW: that update reads W from d_shadow.  shadow_valid: the leading slots whose
+  // shadow holds (float) of the block as it stands; whoever writes a basis block outside the
+  // step's own pattern (slots >= i - 2 in step i) lowers it (shadow_written)
+  int shadow_opt = 1;
+  int shadow_valid = 0;
+  int64_t shadow_slot = 0;  // floats per shadow slot
+  size_t shadow_bytes = 0;
   bool plan_all_resident = false;  // this run was started with RBL_OPT_DEVICE_BLOCKS = 0
   std::vector<int> step_flags;  // part_reorth flags per step (the fusion's schedule guess)
   double stage_ms[RBL_NUM_STAGES] = {0};
@@ -466,6 +477,8 @@ double* slotp(rbl_ctx* ctx, int j) {
   return ctx->d_basis + (int64_t)s * ctx->slot;
 }
 bool spilled(const rbl_ctx* ctx) { return ctx->resident != INT32_MAX; }
+// basis slots >= lowest are (about to be) written: their shadow no longer holds (float) of them
+void shadow_written(rbl_ctx* ctx, int lowest) { ctx->shadow_valid = std::min(ctx->shadow_valid, std::max(lowest, 0)); }
 // fp64 block j on the device: in place when resident or among the newest two of `nblocks`,
 // else copied from pinned host memory into the staging block (on the compute stream)
 const double* block_dev(rbl_ctx* ctx, int j, int nblocks, int* st) {
@@ -1995,6 +2008,9 @@ int reorth_pair(rbl_ctx* ctx, int i, int flags) {
   const int b = ctx->b;
   double* Qi = slotp(ctx, i - 1);
   double* Qm = i >= 2 ? slotp(ctx, i - 2) : nullptr;
+  // whatever route: only slots i - 1 and i - 2 are written (a step never has a valid shadow there;
+  // rbl_reorth_last may be asked for an earlier pair)
+  shadow_written(ctx, i - 2);
   if ((flags & 2) && ctx->nlock > 0) {
     StageScope t(ctx, RBL_STAGE_PART_REORTH);
     if (Qm) CHK(lock_reorth(ctx, Qm));
@@ -2047,7 +2063,17 @@ int reorth_pair(rbl_ctx* ctx, int i, int flags) {
         HIPC(hipGetLastError());
       }
       if (u32) {
-        tsmm44x32(ctx->nloc, W, ctx->d_C, 2 * b, Yp, ctx->d_upd32, ctx->stream);
+        // RBL_OPT_UPD32_SHADOW: the panels below shadow_valid come from the fp32 shadow, the
+        // others (two per even step of a run) are rounded as ever and enter it — also when the
+        // gate refuses, which the host cannot know: the shadow is valid up to nW either way.
+        // (rbl_reorth_last on a full basis has one panel more than the shadow has slots)
+        if (ctx->d_shadow && ctx->shadow_opt && nW <= ctx->max_blocks - 2) {
+          tsmm44x32_shadow(ctx->nloc, W, ctx->d_C, 2 * b, Yp, ctx->d_upd32, ctx->d_shadow,
+                           ctx->shadow_valid, ctx->d_upd32 + 4, ctx->stream);
+          ctx->shadow_valid = nW;
+        } else {
+          tsmm44x32(ctx->nloc, W, ctx->d_C, 2 * b, Yp, ctx->d_upd32, ctx->stream);
+        }
         HIPC(hipGetLastError());
         CHK(tsmm_checked(ctx, W, ctx->d_C, 2 * b, Yp, -1.0, 1.0, ctx->d_upd32 + 1));
       } else {  // (also a rank whose rows do not fit the fp32 kernel: fp64 whatever the gate says)
@@ -2628,6 +2654,9 @@ void free_run(rbl_ctx* ctx) {
   ctx->nblocks = 0;
   ctx->b = 0;
   ctx->have_bprev = false;
+  ctx->shadow_valid = 0;
+  ctx->shadow_slot = 0;
+  ctx->shadow_bytes = 0;
 }
 
 // the rank-one shift of a rectangular B and the buffers of its reductions
@@ -3056,6 +3085,10 @@ int rbl_set_option(rbl_ctx* ctx, int option, int64_t value) {
     case RBL_OPT_UPD32:
       if (value < 0 || value > 2) return fail(ctx, RBL_ERR_INVALID, "RBL_OPT_UPD32 must be 0|1|2");
       ctx->upd32 = (int)value;
+      return RBL_OK;
+    case RBL_OPT_UPD32_SHADOW:
+      if (value < 0 || value > 1) return fail(ctx, RBL_ERR_INVALID, "RBL_OPT_UPD32_SHADOW must be 0|1");
+      ctx->shadow_opt = (int)value;
       return RBL_OK;
     default: return fail(ctx, RBL_ERR_INVALID, "unknown option");
   }
@@ -3934,12 +3967,14 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
       const double mine = ctx->d_basis ? (double)(ctx->resident == INT32_MAX ? ctx->max_blocks + 1 : ctx->resident + 2) * blk64
                         : ctx->d_basis32 ? (double)(ctx->resident == INT32_MAX ? ctx->max_blocks + 1 : ctx->resident + 2) * blk64 * 0.5
                         : 0.0;
+      // (the fp32 shadow is freed with the plan and never weighs on the slot count)
+      const double mine_all = mine + (double)ctx->shadow_bytes;
       // U, T (+ the halo buffer on several ranks; + the fp32 path's fp64 Q_i, and Q_{i-1}
       // when the SpMM cannot read fp32), one staging block, the Gram slab
       const double work = 2.0 + (ctx->nranks > 1 ? 1.0 : 0.0) +
                           (basis_bits == 32 ? 1.0 + (direct32_ok(ctx, b) ? 0.0 : 1.0) : 0.0);
       const double other = work * blk64 + blk + 8.0 * (double)gram_slab_elems(ctx, b, max_blocks, basis_bits);
-      g = (int)std::max(3.0, std::floor((0.8 * ((double)fr + mine) - other) / blk));
+      g = (int)std::max(3.0, std::floor((0.8 * ((double)fr + mine_all) - other) / blk));
     }
     dev_slots = std::min(dev_slots, std::max(3, g));
   }
@@ -3948,6 +3983,7 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   ctx->nlock = 0;  // a new problem: no locked vectors
   ctx->arrow_kb = 0;
   ctx->cloc_step = 0;
+  ctx->shadow_valid = 0;
   ctx->step_flags.clear();
   // the allocations below fail alone on one rank (its HBM): every rank then learns of it before
   // the collectives of the start, and all return the error, instead of the peers waiting in the
@@ -4011,8 +4047,8 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   HIPC(ctx->d_flags.alloc(6));
   HIPC(hipMemset(ctx->d_flags, 0, 6 * sizeof(int)));
   if (!ctx->d_upd32) {  // kept across runs: its counters are rbl_path_stats entries
-    HIPC(ctx->d_upd32.alloc(4));
-    HIPC(hipMemset(ctx->d_upd32, 0, 4 * sizeof(int)));
+    HIPC(ctx->d_upd32.alloc(6));
+    HIPC(hipMemset(ctx->d_upd32, 0, 6 * sizeof(int)));
     HIPC(ctx->d_upd32_g.alloc(kUpd32Log));
     HIPC(hipMemset(ctx->d_upd32_g, 0, kUpd32Log * sizeof(double)));
   }
@@ -4035,6 +4071,24 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
       HIPC(hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->dv_hist), ctx->h_hist, 0));
     } else {
       HIPC(ctx->d_stash.alloc(stash_rec(b)));
+    }
+  }
+  // RBL_OPT_UPD32_SHADOW, after everything the run needs: only where the fp32 update can run
+  // (fp64 basis, b = 32, RBL_OPT_UPD32 on, every block in HBM) and only into memory the fit rule
+  // leaves over.  Kept with the plan (a reused plan allocates nothing), freed by free_run.  A rank
+  // that goes without takes the fp64-basis loads: no collective and no bit differs.
+  if (ctx->shadow_opt && ctx->upd32 != 0 && basis_bits == 64 && b == 32 && !spilled(ctx) &&
+      max_blocks >= 3 && ctx->nloc > 0) {
+    const int64_t sslot = tsmm44x32_shadow_slot(ctx->nloc);
+    const size_t need = (size_t)(max_blocks - 2) * (size_t)sslot * sizeof(float);
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) == hipSuccess && rbl_plan_shadow_fits(fr, tot, need)) {
+      if (ctx->d_shadow.alloc((size_t)(max_blocks - 2) * (size_t)sslot) == hipSuccess) {
+        ctx->shadow_slot = sslot;
+        ctx->shadow_bytes = need;
+      } else {
+        (void)hipGetLastError();  // the run goes on without the shadow
+      }
     }
   }
   }
@@ -5658,6 +5712,7 @@ int rbl_num_blocks(rbl_ctx* ctx) { return ctx ? ctx->nblocks : 0; }
 // ---- restarted variants (restarted.jl) -------------------------------------------------
 int rbl_restart(rbl_ctx* ctx, int nblocks, const double* S) {
   if (ctx) ctx->cloc_step = 0;  // the basis changes outside the step
+  if (ctx) shadow_written(ctx, 0);
   if (ctx) ctx->arrow_kb = 0;
   if (!ctx || !S || nblocks < 1 || nblocks > ctx->nblocks)
     return fail(ctx, RBL_ERR_INVALID, "rbl_restart: bad arguments");
@@ -5745,6 +5800,7 @@ int rbl_thick_restart(rbl_ctx* ctx, int nblocks, int keep_blocks, const double* 
   harvest_timers(ctx);
   ctx->cloc_step = 0;  // the basis changes outside the step
   ctx->cloc_final = false;
+  shadow_written(ctx, 0);  // the compression rewrote slots 0 .. kb
   ctx->nblocks = kb + 1;
   ctx->fetched = kb + 1;
   ctx->arrow_kb = kb;
@@ -5806,6 +5862,7 @@ int rbl_bench_compress_pass(rbl_ctx* ctx, int64_t rows, int b, int m, int keep_b
 
 int rbl_lock(rbl_ctx* ctx, int nblocks, int nvec, const double* S) {
   if (ctx) ctx->cloc_step = 0;  // the basis changes outside the step
+  if (ctx) shadow_written(ctx, 0);  // (a restart follows a lock: nothing of the shadow is kept)
   if (!ctx || !S || nblocks < 1 || nblocks > ctx->nblocks || nvec < 0)
     return fail(ctx, RBL_ERR_INVALID, "rbl_lock: bad arguments");
   if (!ctx->d_basis) return fail(ctx, RBL_ERR_STATE, "rbl_lock: needs an fp64 run (rbl_start)");
@@ -5902,17 +5959,34 @@ int rbl_path_stats(rbl_ctx* ctx, int64_t* out, int nstats, int reset) {
   if (!ctx || nstats < 0 || (nstats > 0 && !out)) return RBL_ERR_INVALID;
   // the fp32-update gate counts on the device (k_upd32_gate): read back behind the stream
   if (ctx->d_upd32) {
-    int cnt[2] = {0, 0};
+    int cnt[4] = {0, 0, 0, 0};
     HIPC(hipSetDevice(ctx->device));
     HIPC(hipStreamSynchronize(ctx->stream));
     HIPC(hipMemcpy(cnt, ctx->d_upd32 + 2, sizeof(cnt), hipMemcpyDeviceToHost));
     ctx->path_stats[RBL_PATH_UPD32_TAKEN] = cnt[0];
     ctx->path_stats[RBL_PATH_UPD32_REFUSED] = cnt[1];
+    ctx->path_stats[RBL_PATH_UPD32_SHADOW_READ] = cnt[2];
+    ctx->path_stats[RBL_PATH_UPD32_SHADOW_CONV] = cnt[3];
     if (reset) HIPC(hipMemset(ctx->d_upd32 + 2, 0, sizeof(cnt)));
   }
+  ctx->path_stats[RBL_PATH_UPD32_SHADOW_BYTES] = (int64_t)ctx->shadow_bytes;  // the plan's, not a count
   for (int i = 0; i < nstats; ++i) out[i] = i < RBL_PATH_NSTATS ? ctx->path_stats[i] : 0;
   if (reset)
     for (int64_t& v : ctx->path_stats) v = 0;
+  return RBL_OK;
+}
+
+int rbl_shadow_valid(rbl_ctx* ctx) { return ctx && ctx->d_shadow ? ctx->shadow_valid : 0; }
+
+int rbl_get_shadow_block(rbl_ctx* ctx, int j, float* out) {
+  if (!ctx || !out || !ctx->d_shadow || j < 1 || j > ctx->shadow_valid)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_get_shadow_block: no valid shadow of that block");
+  HIPC(hipSetDevice(ctx->device));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  std::vector<float> slot((size_t)ctx->shadow_slot);
+  HIPC(hipMemcpy(slot.data(), ctx->d_shadow + (int64_t)(j - 1) * ctx->shadow_slot,
+                 slot.size() * sizeof(float), hipMemcpyDeviceToHost));
+  shadow_block_rowmajor(slot.data(), ctx->nloc, out);
   return RBL_OK;
 }
 

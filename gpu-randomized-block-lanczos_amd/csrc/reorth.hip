@@ -9,7 +9,8 @@
 //                (RBL_gpu.jl:34,40), the 3-term / local-reorth updates, CholQR apply and the
 //                Ritz projection V = [Q_1..Q_m] S (RBL_gpu.jl:121, RBL.jl:68).
 // And one fp32-MFMA kernel over the same fp64 data, k_tsmm44x32: the partial-reorth update where
-// its coefficients are rounding residue (RBL_OPT_UPD32).
+// its coefficients are rounding residue (RBL_OPT_UPD32), with a form that reads W from an fp32
+// shadow it fills itself (RBL_OPT_UPD32_SHADOW).
 //
 // v_mfma_f64_4x4x4f64 lane layout (tools/mfma_layout_probe.hip), block g = (lane>>2)&3:
 //   A[i = lane&3][k = lane>>4], B[k = lane>>4][j = lane&3], D[i = lane>>4][j = lane&3].
@@ -969,11 +970,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kT44fNrt ==
 typedef float f2v32 __attribute__((ext_vector_type(2)));
 typedef float f4v32 __attribute__((ext_vector_type(4)));
 constexpr int kU32Rows = 32;  // rows per wave (k_tsmm44x32)
+// The fp32 shadow of W (SH; RBL_OPT_UPD32_SHADOW): a basis block never changes once it is part of
+// W, so (float)w is formed once and kept.  Panels ch < nsh are read from the shadow S as fp32 (half
+// the bytes, no conversion); panels ch >= nsh ("fresh") are loaded as fp64 and rounded as without
+// the shadow, and the rounded values are stored to S for the later steps.  The MFMAs see the same
+// values in the same lanes in the same order, so Y has the bits of the form without the shadow.
+// With the skip flag set (the gate chose the fp64 kernel, which the host cannot know) the fresh
+// panels are still rounded and stored, no product is formed and Y is left alone.
+// cnt (block 0): [0] += panels read from the shadow, [1] += panels rounded into it.
+// Layout of a shadow slot (this kernel's own; shadow_block_rowmajor undoes it): tiles of 32 rows x
+// 32 k = 256 float4, tile t = rows 32 t .. 32 t + 31, padded to whole tiles (shadow_slot_floats).
+// float4 ((2 rt + hf) 64 + 16 q + c16) of a tile holds row 32 t + 16 rt + c16 at
+// k = 8 (2 hf + e / 2) + 2 q + e % 2, e = 0 .. 3: the MFMA A operands of lane (q, c16) for row tile
+// rt and steps (h, v) = (2 hf + e / 2, e % 2).  A wave on an aligned tile moves 1 KiB contiguous
+// per instruction, 16 B per lane, four instructions per chunk.  The shifted last wave (rw < r0, rw
+// no multiple of 32) finds each of its rows in one of two tiles, per lane; it stores rows that the
+// wave before it stores too — both hold the same (float)w, so the order does not matter.
+__host__ __device__ inline int64_t shadow_slot_floats(int64_t nrows) { return (nrows + 31) / 32 * 1024; }
+template <bool SH>
 __global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
                                                    const double* __restrict__ C, int ldc, double* Y0,
-                                                   double* Y1, const int* skip) {
-  if (skip && *skip) return;
+                                                   double* Y1, const int* skip, float* S, int nsh,
+                                                   int* cnt) {
   constexpr int W = 32, KYP = 64, CT = 4, CLD = 64, KF = 32, NH = KF / 8, OLD = KYP + 4;
+  const bool skipped = skip && *skip;
+  if (!SH && skipped) return;
   // two C buffers; after the k-loop the same LDS holds the 4 waves' 16 x (64 + 4) fp32 tiles
   __shared__ __attribute__((aligned(16))) float cs[2][KF * CLD + 128];
   static_assert(2 * (KF * CLD + 128) >= 4 * 16 * OLD, "epilogue tiles fit");
@@ -1026,17 +1047,78 @@ __global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
           f4v32{cr[hh][0], cr[hh][1], cr[hh][2], cr[hh][3]};
   };
 
+  // the shadow: this lane's two float4 (hf = 0, 1) of row rw + 16 rt + c16 start at soff[rt]
+  const int64_t sslot = shadow_slot_floats(nrows);
+  unsigned soff[2];
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt) {
+    const int64_t r = rw + 16 * rt + c16;
+    soff[rt] = (unsigned)((r >> 5) * 1024 + (((r >> 4) & 1) * 128 + 16 * q + (r & 15)) * 4);
+  }
+  // (a shadow chunk is prefetched into the registers of the fp64 one: never both in flight)
+  auto load_s = [&](int ch, d2v (&ar)[2][NH]) {
+    const float* sb = S + (int64_t)ch * sslot;  // uniform
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+        ar[rt][hf] = __builtin_bit_cast(d2v, *reinterpret_cast<const f4v32*>(sb + (soff[rt] + 256u * hf)));
+  };
+  auto take_s = [&](const d2v (&ar)[2][NH], float (&af)[2][NH][2]) {
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int h = 0; h < NH; ++h) {
+        const f4v32 sr = __builtin_bit_cast(f4v32, ar[rt][h >> 1]);
+        af[rt][h][0] = sr[2 * (h & 1)];
+        af[rt][h][1] = sr[2 * (h & 1) + 1];
+      }
+  };
+  auto store_s = [&](int ch, const float (&af)[2][NH][2]) {
+    float* sb = S + (int64_t)ch * sslot;
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+        *reinterpret_cast<f4v32*>(sb + (soff[rt] + 256u * hf)) =
+            f4v32{af[rt][2 * hf][0], af[rt][2 * hf][1], af[rt][2 * hf + 1][0], af[rt][2 * hf + 1][1]};
+  };
+
   d2v anext[2][NH];
   float af[2][NH][2];
   float cr[2][CT];
+  if constexpr (SH) {
+    if (blockIdx.x == 0 && tid == 0) {  // kernels of one stream: no other writer
+      cnt[0] += skipped ? 0 : nsh;
+      cnt[1] += nch - nsh;
+    }
+    if (skipped) {  // the fp64 kernel forms Y; the fresh panels enter the shadow all the same
+      for (int ch = nsh; ch < nch; ++ch) {
+        load_a(ch, anext);
+        round_a(anext, af);
+        store_s(ch, af);
+      }
+      return;
+    }
+  }
   load_c(0, cr);
   store_c(0, cr);
-  load_a(0, anext);
-  round_a(anext, af);
+  if (SH && nsh > 0) {
+    load_s(0, anext);
+    take_s(anext, af);
+  } else {
+    load_a(0, anext);
+    round_a(anext, af);
+    if constexpr (SH) store_s(0, af);
+  }
   __syncthreads();
   for (int ch = 0; ch < nch; ++ch) {
     load_c(ch + 1, cr);  // unconditional, clamped (see k_gram44)
-    load_a(ch + 1, anext);
+    // the chunk ahead comes from the shadow or, fresh, from the fp64 basis (uniform; the shadow
+    // panels are the leading ones, so the k order is the ascending one either way)
+    const bool ns = SH && ch + 1 < nsh;
+    if (ns) load_s(ch + 1, anext);
+    else load_a(ch + 1, anext);
     const float* cb = cs[ch & 1] + 2 * q * CLD + 4 * c16;
 #pragma unroll
     for (int hv = 0; hv < 2 * NH; ++hv) {
@@ -1049,7 +1131,13 @@ __global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
           acc[rt][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[rt][h][v], bv[c], acc[rt][c], 0, 0, 0);
     }
     store_c((ch + 1) & 1, cr);
-    round_a(anext, af);
+    if (ns) {
+      take_s(anext, af);
+    } else {
+      round_a(anext, af);
+      if constexpr (SH)
+        if (ch + 1 < nch) store_s(ch + 1, af);
+    }
     __syncthreads();
   }
   // epilogue: D (lane: rows 4 q + v, column c16 of tile c) -> LDS (free after the loop's last
@@ -1094,8 +1182,27 @@ bool tsmm44x32_ok(int64_t nrows, const PanelRun& X, const Panels& Y) {
 void tsmm44x32(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
                const int* skip, hipStream_t st) {
   const int64_t wgs = (nrows + 4 * kU32Rows - 1) / (4 * kU32Rows);
-  hipLaunchKernelGGL(k_tsmm44x32, dim3((unsigned)wgs), dim3(256), 0, st, nrows, X, C, ldc,
-                     const_cast<double*>(Y.ptr[0]), const_cast<double*>(Y.ptr[1]), skip);
+  hipLaunchKernelGGL(k_tsmm44x32<false>, dim3((unsigned)wgs), dim3(256), 0, st, nrows, X, C, ldc,
+                     const_cast<double*>(Y.ptr[0]), const_cast<double*>(Y.ptr[1]), skip, nullptr, 0, nullptr);
+}
+
+int64_t tsmm44x32_shadow_slot(int64_t nrows) { return shadow_slot_floats(nrows); }
+
+void tsmm44x32_shadow(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
+                      const int* skip, float* S, int nsh, int* cnt, hipStream_t st) {
+  const int64_t wgs = (nrows + 4 * kU32Rows - 1) / (4 * kU32Rows);
+  hipLaunchKernelGGL(k_tsmm44x32<true>, dim3((unsigned)wgs), dim3(256), 0, st, nrows, X, C, ldc,
+                     const_cast<double*>(Y.ptr[0]), const_cast<double*>(Y.ptr[1]), skip, S,
+                     std::min(std::max(nsh, 0), X.count), cnt);
+}
+
+void shadow_block_rowmajor(const float* slot, int64_t nrows, float* out) {
+  for (int64_t r = 0; r < nrows; ++r)
+    for (int k = 0; k < 32; ++k) {
+      const int h = k >> 3, q = (k & 7) >> 1, v = k & 1;
+      const int64_t f4 = (r >> 5) * 256 + ((r >> 4) & 1) * 128 + (h >> 1) * 64 + 16 * q + (r & 15);
+      out[r * 32 + k] = slot[f4 * 4 + 2 * (h & 1) + v];
+    }
 }
 
 // the epilogue stores Y row-major 16 B (two columns) per lane: Y panel widths must be even

@@ -38,6 +38,7 @@ RBL_OPT_RELABEL = 8
 RBL_OPT_HALO_PUSH = 9
 RBL_OPT_CLOC_DERIVE = 10
 RBL_OPT_UPD32 = 11
+RBL_OPT_UPD32_SHADOW = 12
 # rbl_path_stats entries
 RBL_PATH_SPMM = 0
 RBL_PATH_SPMM_LOC_FUSED = 1
@@ -51,7 +52,10 @@ RBL_PATH_CLOC_3TERM = 8
 RBL_PATH_CLOC_REORTH = 9
 RBL_PATH_UPD32_TAKEN = 10
 RBL_PATH_UPD32_REFUSED = 11
-RBL_PATH_NSTATS = 12
+RBL_PATH_UPD32_SHADOW_READ = 12
+RBL_PATH_UPD32_SHADOW_CONV = 13
+RBL_PATH_UPD32_SHADOW_BYTES = 14
+RBL_PATH_NSTATS = 15
 RBL_BUILD_VARIANTS = 1
 # a rectangular B (rbl_set_matrix_normal): what rbl_spmm_kernel_for / rbl_matrix_format report
 RBL_SPMM_KERNEL_RECT = 8
@@ -171,12 +175,15 @@ SIGNATURES = {
     "rbl_comm_stats": (C.c_int, [_p, _pi64, C.c_int, C.c_int]),
     "rbl_path_stats": (C.c_int, [_p, _pi64, C.c_int, C.c_int]),
     "rbl_upd32_gate_values": (C.c_int, [_p, _pd, C.c_int]),
+    "rbl_shadow_valid": (C.c_int, [_p]),
+    "rbl_get_shadow_block": (C.c_int, [_p, C.c_int, C.POINTER(C.c_float)]),
     "rbl_allgather_host":(C.c_int, [_p, _pi64, _pi64, C.c_int]),
     "rbl_synchronize": (C.c_int, [_p]),
     "rbl_plan_row_partition": (C.c_int, [_i64, _pi64, C.c_int, _pi64]),
     "rbl_plan_halo": (C.c_int, [_i64, _pi64, _pi64, C.c_int, C.c_int, _pi64, _pi64, _pi64]),
     "rbl_hashwindow_rows_host": (C.c_int, [_i64, _i64, C.c_double, _u64, C.c_int, _pd, _i64,
                                            _i64, _pi64, _pi64, _pd]),
+    "rbl_plan_shadow_fits": (C.c_int, [_u64, _u64, _u64]),
 }
 
 
@@ -241,6 +248,11 @@ def plan_row_partition(rowptr: np.ndarray, nranks: int) -> np.ndarray:
     if st != RBL_OK:
         raise RBLError(st, "rbl_plan_row_partition")
     return out
+
+
+def plan_shadow_fits(free_bytes: int, total_bytes: int, needed_bytes: int) -> bool:
+    """The fit rule of RBL_OPT_UPD32_SHADOW (rbl_plan_shadow_fits; no GPU needed)."""
+    return bool(lib.rbl_plan_shadow_fits(int(free_bytes), int(total_bytes), int(needed_bytes)))
 
 
 def plan_halo(rowptr, colind, bounds, index_base=0):

@@ -772,20 +772,39 @@ class Context:
         coefficients taken from the 3-term pass or derived through the partial reorth
         (RBL_OPT_CLOC_DERIVE).  upd32_taken / upd32_refused: partial-reorth updates the device
         gate sent to the fp32-MFMA kernel or kept on the fp64 one (RBL_OPT_UPD32), counted on the
-        device and read back after a stream synchronise."""
+        device and read back after a stream synchronise; upd32_shadow_read / upd32_shadow_conv:
+        basis panels that kernel read from the fp32 shadow / rounded and stored to it
+        (RBL_OPT_UPD32_SHADOW, device counts too); upd32_shadow_bytes: the bytes of the shadow the
+        current run plan holds (0: none; not a counter, a reset leaves it)."""
         from . import _lib as L
         out = np.zeros(L.RBL_PATH_NSTATS, np.int64)
         self._check(lib.rbl_path_stats(self._h, i64ptr(out), L.RBL_PATH_NSTATS, int(reset)),
                     "rbl_path_stats")
         return dict(zip(("spmm", "spmm_loc_fused", "loc_separate", "loc_gram", "locfix_edges",
                          "locfix_rest", "spmm_two_wave", "ritz_pieces", "cloc_3term",
-                         "cloc_reorth", "upd32_taken", "upd32_refused"), (int(x) for x in out)))
+                         "cloc_reorth", "upd32_taken", "upd32_refused", "upd32_shadow_read",
+                         "upd32_shadow_conv", "upd32_shadow_bytes"), (int(x) for x in out)))
 
     def upd32_gate_values(self) -> np.ndarray:
         """Diagnostics (rbl_upd32_gate_values): the RBL_OPT_UPD32 gate's g of block step i at
         [i % 64], 0 where the gate has not run."""
         out = np.zeros(64, np.float64)
         self._check(lib.rbl_upd32_gate_values(self._h, dptr(out), 64), "rbl_upd32_gate_values")
+        return out
+
+    def shadow_valid(self) -> int:
+        """Diagnostics (rbl_shadow_valid): the leading blocks whose fp32 shadow is current
+        (RBL_OPT_UPD32_SHADOW; 0 without a shadow)."""
+        return int(lib.rbl_shadow_valid(self._h))
+
+    def get_shadow_block(self, j: int) -> np.ndarray:
+        """Diagnostics (rbl_get_shadow_block): the fp32 shadow of block j (1-based as get_block,
+        j <= shadow_valid()), n_local x 32."""
+        import ctypes as C
+        n, r0, r1, _ = self.matrix_info()
+        out = np.zeros((r1 - r0, 32), np.float32)
+        self._check(lib.rbl_get_shadow_block(self._h, j, out.ctypes.data_as(C.POINTER(C.c_float))),
+                    "rbl_get_shadow_block")
         return out
 
     def allgather(self, values) -> np.ndarray:

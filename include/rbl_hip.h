@@ -171,6 +171,18 @@ extern "C" {
                                    * RBL_OPT_CLOC_DERIVE route of that step, no locked vectors;
                                    * everything else keeps the fp64 update.  Counted in
                                    * rbl_path_stats (RBL_PATH_UPD32_TAKEN / _REFUSED). */
+#define RBL_OPT_UPD32_SHADOW  12  /* 1 (default): the fp32 update of RBL_OPT_UPD32 reads W from an
+                                   * fp32 shadow of the basis, max_blocks - 2 slots of n_local x 32
+                                   * floats beside it: a block never changes once it is part of W,
+                                   * so (float)w is formed once — by the update that first meets
+                                   * the block, which stores what it rounds — and every later update
+                                   * fetches 4 bytes per entry instead of 8.  Results do not change
+                                   * by a bit.  Read by rbl_start when it plans a run: the shadow is
+                                   * allocated for an fp64 basis at b = 32 with RBL_OPT_UPD32 != 0
+                                   * and every block in HBM, when it fits beside the basis
+                                   * (rbl_plan_shadow_fits), and kept while the plan is reused.  0, or
+                                   * any of these unmet, or the allocation failing: the update reads
+                                   * the fp64 basis as before.  RBL_PATH_UPD32_SHADOW_* count it. */
 
 typedef struct rbl_ctx rbl_ctx;
 
@@ -794,11 +806,23 @@ int rbl_allgather_host(rbl_ctx* ctx, const int64_t* mine, int64_t* all, int n);
                                        kernel (RBL_OPT_UPD32) ...                              */
 #define RBL_PATH_UPD32_REFUSED   11 /* ... and those it kept on the fp64 kernel; both counted on
                                        the device and read back behind the context's stream    */
-#define RBL_PATH_NSTATS          12
+#define RBL_PATH_UPD32_SHADOW_READ  12 /* basis panels the fp32 update read from the fp32
+                                          shadow (RBL_OPT_UPD32_SHADOW) ...                    */
+#define RBL_PATH_UPD32_SHADOW_CONV  13 /* ... and panels it rounded and stored to it; both counted
+                                          on the device like the two above                     */
+#define RBL_PATH_UPD32_SHADOW_BYTES 14 /* bytes of the shadow the current run plan holds (0: none;
+                                          a state, not a counter: a reset leaves it)           */
+#define RBL_PATH_NSTATS          15
 int rbl_path_stats(rbl_ctx* ctx, int64_t* out, int nstats, int reset);
 /* Diagnostics: the value g of the RBL_OPT_UPD32 gate at block step i in out[i % 64] (n <= 64
  * entries; 0 where the gate has not run).  Waits for the context's stream. */
 int rbl_upd32_gate_values(rbl_ctx* ctx, double* out, int n);
+/* Diagnostics of RBL_OPT_UPD32_SHADOW: the number of leading blocks whose shadow slot holds
+ * (float) of the block as it stands (0 without a shadow), and the shadow of block j (1-based as
+ * rbl_get_block, j <= rbl_shadow_valid) as n_local x 32 floats ROW-major, whatever the layout on
+ * the device.  Both wait for the context's stream. */
+int rbl_shadow_valid(rbl_ctx* ctx);
+int rbl_get_shadow_block(rbl_ctx* ctx, int j, float* out);
 
 /* ---- host-only planning (callable without a GPU) -------------------------------------- */
 /* nnz-balanced contiguous row partition: bounds_out[0..nranks] (bounds_out[0]=0). */
@@ -813,6 +837,10 @@ int rbl_hashwindow_rows_host(int64_t n, int64_t halfwidth, double density, uint6
                              int nplant, const double* plant, int64_t row_begin,
                              int64_t row_end, int64_t* rowptr_out, int64_t* colind_out,
                              double* val_out);
+/* The fit rule of RBL_OPT_UPD32_SHADOW: 1 when a shadow of needed_bytes may be allocated on a
+ * device that reports free_bytes of total_bytes free (hipMemGetInfo, after the basis and the run's
+ * other buffers): it fits and a tenth of the device stays free.  Never changes the basis plan. */
+int rbl_plan_shadow_fits(uint64_t free_bytes, uint64_t total_bytes, uint64_t needed_bytes);
 
 #ifdef __cplusplus
 }

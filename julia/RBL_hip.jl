@@ -37,6 +37,7 @@ const librbl_hip = get(ENV, "RBL_HIP_LIB", "librbl_hip.so")
 const RBL_OPT_TIMERS = Cint(0)
 const RBL_OPT_DEVICE_BLOCKS = Cint(3)
 const RBL_OPT_UPD32 = Cint(11)  # 0 off, 1 gated on the device (default), 2 always (tests only)
+const RBL_OPT_UPD32_SHADOW = Cint(12)  # 1 (default): that update reads an fp32 shadow of the basis when it fits; 0 off
 const RBL_WARN_QR_SHIFTED = Cint(2)
 
 struct RblError <: Exception
