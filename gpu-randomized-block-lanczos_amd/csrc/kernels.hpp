@@ -524,12 +524,16 @@ int tsmm44_xg_grid(int64_t nrows);
 void tsmm44(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
             double alpha, double beta, const int* skip, hipStream_t s, double* xslab = nullptr,
             int* xgrid = nullptr);
-// [Y0 | Y1] -= X C with the products rounded to fp32 and summed on fp32 MFMA (k_tsmm44x32): X fp64
-// panels of 32, Y two fp64 panels of 32, C fp64 row-major; for coefficients C of rounding size
-// only (upd32_gate).  tsmm44x32_ok: the shapes it takes (nrows >= 32, no aliasing).
+// [Y0 | Y1] -= X C with both factors rounded to fp32, each split into three bf16 pieces, and six
+// piece products per k summed in fp32 on bf16 MFMA (k_tsmm44x32): X fp64 panels of 32, Y two fp64
+// panels of 32, C fp64 row-major; for coefficients C of rounding size only (upd32_gate).
+// tsmm44x32_ok: the shapes it takes (nrows >= 32, no aliasing).  Cp: workspace of
+// tsmm44x32_cpieces(K) 16-bit units (K = 32 X.count), 16-B aligned: the split image of C, written
+// by a small kernel ahead of the update on the same stream.
 bool tsmm44x32_ok(int64_t nrows, const PanelRun& X, const Panels& Y);
+int64_t tsmm44x32_cpieces(int K);
 void tsmm44x32(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
-               const int* skip, hipStream_t s);
+               const int* skip, unsigned short* Cp, hipStream_t s);
 // The same update with an fp32 shadow of X (RBL_OPT_UPD32_SHADOW): S holds X.count slots of
 // tsmm44x32_shadow_slot(nrows) floats in the kernel's own layout; the leading nsh panels are read
 // from S, the others from X as above and their rounded values stored to S — also when *skip is set,
@@ -538,7 +542,7 @@ void tsmm44x32(int64_t nrows, const PanelRun& X, const double* C, int ldc, const
 // as nrows x 32 row-major.
 int64_t tsmm44x32_shadow_slot(int64_t nrows);
 void tsmm44x32_shadow(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
-                      const int* skip, float* S, int nsh, int* cnt, hipStream_t s);
+                      const int* skip, float* S, int nsh, int* cnt, unsigned short* Cp, hipStream_t s);
 void shadow_block_rowmajor(const float* slot, int64_t nrows, float* out);
 
 // --- reorth32.hip: the fp32 Krylov basis (mixed precision, b in {16, 32}) ---------------

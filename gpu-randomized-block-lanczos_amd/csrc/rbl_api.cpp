@@ -226,6 +226,7 @@ struct RunBufs {
   DevBuf<double> d_precv;    // n_send x b: partial rows received for own rows
   DevBuf<double> d_slab;
   DevBuf<double> d_C;        // Gram result (<= (max_blocks)*b x 2b)
+  DevBuf<unsigned short> d_C16;  // b = 32: d_C as the three bf16 images of k_tsmm44x32 (RBL_OPT_UPD32)
   DevBuf<double> d_small;    // R, Rinv, Rtot, Bprev, Ai, G (b x b each)
   DevBuf<int> d_flags;       // [need3, skip3, status0, status1, cloc derived, cloc direct]
   PinBuf<double> h_pin;      // pinned staging: Ai, Rtot (2 b x b)
@@ -2069,10 +2070,10 @@ int reorth_pair(rbl_ctx* ctx, int i, int flags) {
         // (rbl_reorth_last on a full basis has one panel more than the shadow has slots)
         if (ctx->d_shadow && ctx->shadow_opt && nW <= ctx->max_blocks - 2) {
           tsmm44x32_shadow(ctx->nloc, W, ctx->d_C, 2 * b, Yp, ctx->d_upd32, ctx->d_shadow,
-                           ctx->shadow_valid, ctx->d_upd32 + 4, ctx->stream);
+                           ctx->shadow_valid, ctx->d_upd32 + 4, ctx->d_C16, ctx->stream);
           ctx->shadow_valid = nW;
         } else {
-          tsmm44x32(ctx->nloc, W, ctx->d_C, 2 * b, Yp, ctx->d_upd32, ctx->stream);
+          tsmm44x32(ctx->nloc, W, ctx->d_C, 2 * b, Yp, ctx->d_upd32, ctx->d_C16, ctx->stream);
         }
         HIPC(hipGetLastError());
         CHK(tsmm_checked(ctx, W, ctx->d_C, 2 * b, Yp, -1.0, 1.0, ctx->d_upd32 + 1));
@@ -4042,6 +4043,7 @@ int rbl_start(rbl_ctx* ctx, int b, int max_blocks, int basis_bits, const double*
   HIPC(ctx->d_slab.alloc(slab));
   ctx->C_elems = (size_t)std::max(1, max_blocks) * b * 2 * b;
   HIPC(ctx->d_C.alloc(ctx->C_elems));
+  if (b == 32) HIPC(ctx->d_C16.alloc((size_t)tsmm44x32_cpieces(std::max(1, max_blocks) * b)));  // (k_tsmm44x32's image of d_C)
   HIPC(ctx->d_small.alloc((size_t)S_NSMALL * b * b));
   HIPC(hipMemset(ctx->d_small, 0, (size_t)S_NSMALL * b * b * sizeof(double)));  // (S_CX is summed before it is first written)
   HIPC(ctx->d_flags.alloc(6));

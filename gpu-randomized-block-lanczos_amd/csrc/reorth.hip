@@ -8,9 +8,10 @@
 //   * k_tsmm44:  Y = beta Y + alpha X C  with X a run of panels — the partial-reorth update
 //                (RBL_gpu.jl:34,40), the 3-term / local-reorth updates, CholQR apply and the
 //                Ritz projection V = [Q_1..Q_m] S (RBL_gpu.jl:121, RBL.jl:68).
-// And one fp32-MFMA kernel over the same fp64 data, k_tsmm44x32: the partial-reorth update where
-// its coefficients are rounding residue (RBL_OPT_UPD32), with a form that reads W from an fp32
-// shadow it fills itself (RBL_OPT_UPD32_SHADOW).
+// And one kernel that sums in fp32 over the same fp64 data, k_tsmm44x32 (bf16 MFMA on the three
+// bf16 pieces of each fp32 factor): the partial-reorth update where its coefficients are rounding
+// residue (RBL_OPT_UPD32), with a form that reads W from an fp32 shadow it fills itself
+// (RBL_OPT_UPD32_SHADOW).
 //
 // v_mfma_f64_4x4x4f64 lane layout (tools/mfma_layout_probe.hip), block g = (lane>>2)&3:
 //   A[i = lane&3][k = lane>>4], B[k = lane>>4][j = lane&3], D[i = lane>>4][j = lane&3].
@@ -954,22 +955,94 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kT44fNrt ==
 }
 
 // ----------------------------------------------------------------------------------------
-// [Y0 | Y1] -= W C with the products on fp32 MFMA (v_mfma_f32_16x16x4_f32): the partial-reorth
-// update when its coefficients are rounding residue (k_upd32_gate decides).  W (fp64,
-// panels of 32) and Y (fp64, two panels of 32) stay in HBM as they are; W is rounded to fp32 in
-// registers after the load, C is staged in LDS as (float)C, the 32 x 64 product of a wave is
-// summed in fp32 and subtracted from Y in fp64.  With |C| ~ eps the fp32 rounding of W C,
-// 2^-24 sqrt(K) |W| |C|, stays below the fp64 rounding of Y - W C itself.
+// [Y0 | Y1] -= W C with the products of fp32 factors summed in fp32 on the matrix cores: the
+// partial-reorth update when its coefficients are rounding residue (k_upd32_gate decides; DESIGN
+// §3).  W (fp64, panels of 32) and Y (fp64, two panels of 32) stay in HBM as they are; W is rounded
+// to fp32 in registers after the load, C is rounded to (float)C on its way to LDS, the 32 x 64
+// product of a wave is summed in fp32 and subtracted from Y in fp64.  With |C| ~ eps the fp32
+// rounding of W C, 2^-24 sqrt(K) |W| |C|, stays below the fp64 rounding of Y - W C itself.
+// The products run on v_mfma_f32_16x16x32_bf16 (16 x the fp32 MFMA rate; the fp32 pipe could not
+// keep up with HBM once K passes ~350): an fp32 number is exactly w1 + w2 + w3, w1 = bf16(w),
+// w2 = bf16(w - w1), w3 = w - w1 - w2 (round to nearest even, v_cvt_pk_bf16_f32; both
+// subtractions exact), a product of two bf16 numbers is exact in fp32, and of the nine piece
+// products the six with i + j <= 4 are formed: the three dropped are at most 2^-24 |w| |c| together
+// and ~2^-28 |w| |c| for a typical pair.  Per chunk, row tile and column tile six MFMAs in one fixed order, small pieces
+// first: (w1, c3) (w3, c1) (w2, c2) (w1, c2) (w2, c1) (w1, c1).
 // Shape limits of k_tsmm44f: K a multiple of 32, nrows >= 32, a wave past nrows computes the last
-// 32 rows and stores only its own.  The basis loads are k_tsmm44f's: rows rw + 16 rt + (lane & 15),
-// k = 32 ch + 8 h + 2 q + v as one 16-B load per (rt, h) — 64 contiguous bytes per row and
-// instruction, a wave-uniform base plus a lane constant.  MFMA step (h, v) takes k = 8 h + 2 q + v
-// in lane group q for A and B alike; B[k][16 ct + c16] sits at cs[k][4 c16 + ct] (one
-// ds_read_b128 feeds the four column tiles of both row tiles).
+// 32 rows and stores only its own.  The instruction sums over its 32 k slots whatever k they are
+// labelled with, as long as A and B agree: lane (q = lane >> 4, c16 = lane & 15) holds row
+// rw + 16 rt + c16 in slot j = 2 h + v, j = 0 .. 7, at k = 32 ch + 8 h + 2 q + v.  That keeps
+// k_tsmm44f's basis loads (one 16-B load per (rt, h), 64 contiguous bytes per row and instruction,
+// a wave-uniform base plus a lane constant) and the shadow layout of the fp32 form; with slot j at
+// k = 8 q + j the fp64 loads were 16 B at a 64-B stride and the kernel without the shadow 12 % slower.
+// C: thread (q = tid >> 6, col = tid & 63) rounds and splits C[32 ch + 8 h + 2 q + v][col] and
+// stores one 16-B unit per piece at unit 64 q + col of that piece's 4-KiB image — the B
+// operand of lane (q, c16) for column tile ct is unit 64 q + 16 ct + c16, one ds_read_b128 each,
+// twelve per chunk; a 16-lane read group meets 16 different c16, so no bank is hit twice.
+// RBL_U32_BF16=0 (variants build only, A/B): the same kernel with the products on
+// v_mfma_f32_16x16x4_f32, step j taking slot j in lane group q, C staged as fp32 at
+// cs[k][4 c16 + ct]; same shadow layout.
 // ----------------------------------------------------------------------------------------
+#ifndef RBL_U32_BF16
+#define RBL_U32_BF16 1
+#endif
+// waves per SIMD the register allocation must allow: 3 for the bf16 form (it lands at 123 VGPRs
+// with the shadow, so 4 waves run; with RBL_U32_CDMA=0 it needs 142 and spills when asked for 4),
+// the fp32 form 4 as before
+#ifndef RBL_U32_WPE
+#define RBL_U32_WPE (RBL_U32_BF16 ? 3 : 4)
+#endif
+// RBL_U32_CDMA (default): C is rounded and split once per launch by k_upd32_split_c into the image
+// the k-loop wants, and every workgroup stages a chunk (12 KiB contiguous) by LDS-DMA — no VGPRs, no
+// conversions, no split in the loop.  0 (variants build only, A/B): every workgroup loads, rounds
+// and splits its C chunk itself (140.5 against 124.0 ms per probe sweep)
+#ifndef RBL_U32_CDMA
+#define RBL_U32_CDMA 1
+#endif
 typedef float f2v32 __attribute__((ext_vector_type(2)));
 typedef float f4v32 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
+typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
 constexpr int kU32Rows = 32;  // rows per wave (k_tsmm44x32)
+// w[j] = p[0][j] + p[1][j] + p[2][j] exactly, each piece the bf16 nearest to what the ones before
+// it leave (the last remainder has at most 8 significant bits: its conversion is exact)
+__device__ __forceinline__ void split3_bf16(const float (&w)[8], bf8v (&p)[3]) {
+  float r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = w[j];
+#pragma unroll
+  for (int s = 0; s < 3; ++s)
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {
+      const bf2v b = __builtin_convertvector(f2v32{r[j], r[j + 1]}, bf2v);
+      p[s][j] = b[0];
+      p[s][j + 1] = b[1];
+      if (s < 2) {
+        const f2v32 f = __builtin_convertvector(b, f2v32);
+        r[j] -= f[0];
+        r[j + 1] -= f[1];
+      }
+    }
+}
+// The C image of k_tsmm44x32 (RBL_U32_CDMA): chunk ch (32 k x 64 columns) is 12 KiB at Cp + 6144 ch
+// (16-bit units), piece p at + 2048 p, and in a piece the 16-B unit 64 q + col holds
+// C[32 ch + 8 h + 2 q + v][col] in slot j = 2 h + v — what the chunk's LDS buffer holds.
+// One workgroup per chunk; K / 32 of them.
+constexpr int kU32CpChunk = 3 * 2048;
+__global__ __launch_bounds__(256) void k_upd32_split_c(const double* __restrict__ C, int ldc,
+                                                       unsigned short* __restrict__ Cp, const int* skip) {
+  if (skip && *skip) return;
+  const int tid = threadIdx.x;
+  const double* cb = C + (int64_t)(32 * blockIdx.x + 2 * (tid >> 6)) * ldc + (tid & 63);
+  float cr[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) cr[j] = (float)cb[(int64_t)(8 * (j >> 1) + (j & 1)) * ldc];
+  bf8v cp[3];
+  split3_bf16(cr, cp);
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+    *reinterpret_cast<bf8v*>(Cp + (int64_t)blockIdx.x * kU32CpChunk + 2048 * p + 8 * tid) = cp[p];
+}
 // The fp32 shadow of W (SH; RBL_OPT_UPD32_SHADOW): a basis block never changes once it is part of
 // W, so (float)w is formed once and kept.  Panels ch < nsh are read from the shadow S as fp32 (half
 // the bytes, no conversion); panels ch >= nsh ("fresh") are loaded as fp64 and rounded as without
@@ -981,23 +1054,27 @@ constexpr int kU32Rows = 32;  // rows per wave (k_tsmm44x32)
 // Layout of a shadow slot (this kernel's own; shadow_block_rowmajor undoes it): tiles of 32 rows x
 // 32 k = 256 float4, tile t = rows 32 t .. 32 t + 31, padded to whole tiles (shadow_slot_floats).
 // float4 ((2 rt + hf) 64 + 16 q + c16) of a tile holds row 32 t + 16 rt + c16 at
-// k = 8 (2 hf + e / 2) + 2 q + e % 2, e = 0 .. 3: the MFMA A operands of lane (q, c16) for row tile
-// rt and steps (h, v) = (2 hf + e / 2, e % 2).  A wave on an aligned tile moves 1 KiB contiguous
-// per instruction, 16 B per lane, four instructions per chunk.  The shifted last wave (rw < r0, rw
-// no multiple of 32) finds each of its rows in one of two tiles, per lane; it stores rows that the
-// wave before it stores too — both hold the same (float)w, so the order does not matter.
+// k = 8 (2 hf + e / 2) + 2 q + e % 2, e = 0 .. 3: the two float4 (hf = 0, 1) of lane (q, c16) for
+// row tile rt are slots j = 4 hf + e of its 16x16x32 A operand.  A wave on an aligned tile moves
+// 1 KiB contiguous per instruction, 16 B per lane, four instructions per chunk.  The shifted last
+// wave (rw < r0, rw no multiple of 32) finds each of its rows in one of two tiles, per lane; it
+// stores rows that the wave before it stores too — both hold the same (float)w, so the order does
+// not matter.
 __host__ __device__ inline int64_t shadow_slot_floats(int64_t nrows) { return (nrows + 31) / 32 * 1024; }
 template <bool SH>
-__global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RBL_U32_WPE))) void k_tsmm44x32(int64_t nrows, PanelRun X,
                                                    const double* __restrict__ C, int ldc, double* Y0,
                                                    double* Y1, const int* skip, float* S, int nsh,
-                                                   int* cnt) {
+                                                   int* cnt, const unsigned short* __restrict__ Cp) {
   constexpr int W = 32, KYP = 64, CT = 4, CLD = 64, KF = 32, NH = KF / 8, OLD = KYP + 4;
+  constexpr bool BF = RBL_U32_BF16, CD = BF && RBL_U32_CDMA;
+  // floats per C buffer: three bf16 images of 32 k x 64 columns (4 KiB each), or one fp32 image
+  constexpr int CPC = KF * KYP / 2, CBUF = BF ? 3 * CPC : KF * CLD + 128;
   const bool skipped = skip && *skip;
   if (!SH && skipped) return;
   // two C buffers; after the k-loop the same LDS holds the 4 waves' 16 x (64 + 4) fp32 tiles
-  __shared__ __attribute__((aligned(16))) float cs[2][KF * CLD + 128];
-  static_assert(2 * (KF * CLD + 128) >= 4 * 16 * OLD, "epilogue tiles fit");
+  __shared__ __attribute__((aligned(16))) float cs[2][CBUF];
+  static_assert(2 * CBUF >= 4 * 16 * OLD, "epilogue tiles fit");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q = lane >> 4, c16 = lane & 15;
@@ -1011,6 +1088,7 @@ __global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
 #pragma unroll
     for (int c = 0; c < CT; ++c) acc[rt][c] = f4v32{0.f, 0.f, 0.f, 0.f};
 
+  // fresh panels, k_tsmm44f's loads: slots (2 h, 2 h + 1) of row rw + 16 rt + c16 are one 16-B load
   const unsigned aoff0 = (unsigned)(c16 * W + 2 * q);
   auto load_a = [&](int ch, d2v (&ar)[2][NH]) {
     const int chc = ch < nch ? ch : nch - 1;
@@ -1021,30 +1099,48 @@ __global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
       for (int rt = 0; rt < 2; ++rt)
         ar[rt][h] = *reinterpret_cast<const d2v*>(xb + (aoff0 + (unsigned)(16 * rt * W + 8 * h)));
   };
-  auto round_a = [&](const d2v (&ar)[2][NH], float (&af)[2][NH][2]) {
+  auto round_a = [&](const d2v (&ar)[2][NH], float (&af)[2][8]) {
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
       for (int h = 0; h < NH; ++h) {
-        af[rt][h][0] = (float)ar[rt][h].x;
-        af[rt][h][1] = (float)ar[rt][h].y;
+        af[rt][2 * h] = (float)ar[rt][h].x;
+        af[rt][2 * h + 1] = (float)ar[rt][h].y;
       }
   };
-  // C chunk 32 x 64: thread (k = tid / 16 + 16 hh, cc = tid % 16) moves C[k][cc + 16 ct]
-  const int ck = tid >> 4, ccc = tid & 15;
-  auto load_c = [&](int ch, float (&cr)[2][CT]) {
+  // C chunk 32 x 64: thread (q = tid / 64, column tid % 64) moves C[8 h + 2 q + v][column], slot
+  // j = 2 h + v = 0 .. 7, to unit tid of the three bf16 images; fp32 form: thread (k = tid / 16 +
+  // 16 hh, cc = tid % 16) moves C[k][cc + 16 ct] (cr[4 hh + ct])
+  const int ck = BF ? 2 * (tid >> 6) : tid >> 4, ccc = BF ? tid & 63 : tid & 15;
+  auto load_c = [&](int ch, float (&cr)[8]) {
     const int chc = ch < nch ? ch : nch - 1;
     const double* cb = C + (int64_t)(KF * chc + ck) * ldc + ccc;
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) cr[hh][ct] = (float)cb[(int64_t)(16 * hh) * ldc + 16 * ct];
+    for (int j = 0; j < 8; ++j)
+      cr[j] = (float)cb[BF ? (int64_t)(8 * (j >> 1) + (j & 1)) * ldc
+                           : (int64_t)(16 * (j >> 2)) * ldc + 16 * (j & 3)];
   };
-  auto store_c = [&](int buf, const float (&cr)[2][CT]) {
+  auto store_c = [&](int buf, const float (&cr)[8]) {
+    if constexpr (BF) {
+      bf8v cp[3];
+      split3_bf16(cr, cp);
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh)
-      *reinterpret_cast<f4v32*>(&cs[buf][(ck + 16 * hh) * CLD + 4 * ccc]) =
-          f4v32{cr[hh][0], cr[hh][1], cr[hh][2], cr[hh][3]};
+      for (int p = 0; p < 3; ++p) *reinterpret_cast<bf8v*>(&cs[buf][p * CPC + 4 * tid]) = cp[p];
+    } else {
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh)
+        *reinterpret_cast<f4v32*>(&cs[buf][(ck + 16 * hh) * CLD + 4 * ccc]) =
+            f4v32{cr[4 * hh], cr[4 * hh + 1], cr[4 * hh + 2], cr[4 * hh + 3]};
+    }
+  };
+  // CD: the chunk's image in Cp is the buffer's; each wave moves its 1 KiB of every piece
+  auto dma_c = [&](int buf, int ch) {
+    const int chc = ch < nch ? ch : nch - 1;
+    const unsigned short* src = Cp + (int64_t)chc * kU32CpChunk + 8 * tid;
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+      __builtin_amdgcn_global_load_lds((glb_vptr)(src + 2048 * p), (lds_vptr)(&cs[buf][p * CPC + 256 * wave]), 16,
+                                       0, 0);
   };
 
   // the shadow: this lane's two float4 (hf = 0, 1) of row rw + 16 rt + c16 start at soff[rt]
@@ -1064,29 +1160,36 @@ __global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
       for (int hf = 0; hf < 2; ++hf)
         ar[rt][hf] = __builtin_bit_cast(d2v, *reinterpret_cast<const f4v32*>(sb + (soff[rt] + 256u * hf)));
   };
-  auto take_s = [&](const d2v (&ar)[2][NH], float (&af)[2][NH][2]) {
+  auto take_s = [&](const d2v (&ar)[2][NH], float (&af)[2][8]) {
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-      for (int h = 0; h < NH; ++h) {
-        const f4v32 sr = __builtin_bit_cast(f4v32, ar[rt][h >> 1]);
-        af[rt][h][0] = sr[2 * (h & 1)];
-        af[rt][h][1] = sr[2 * (h & 1) + 1];
+      for (int hf = 0; hf < 2; ++hf) {
+        const f4v32 sr = __builtin_bit_cast(f4v32, ar[rt][hf]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) af[rt][4 * hf + e] = sr[e];
       }
   };
-  auto store_s = [&](int ch, const float (&af)[2][NH][2]) {
+  auto store_s = [&](int ch, const float (&af)[2][8]) {
     float* sb = S + (int64_t)ch * sslot;
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf)
         *reinterpret_cast<f4v32*>(sb + (soff[rt] + 256u * hf)) =
-            f4v32{af[rt][2 * hf][0], af[rt][2 * hf][1], af[rt][2 * hf + 1][0], af[rt][2 * hf + 1][1]};
+            f4v32{af[rt][4 * hf], af[rt][4 * hf + 1], af[rt][4 * hf + 2], af[rt][4 * hf + 3]};
   };
 
   d2v anext[2][NH];
-  float af[2][NH][2];
-  float cr[2][CT];
+  float af[2][8];
+  bf8v ap[2][3];  // the three bf16 pieces of af (BF)
+  auto split_a = [&] {
+    if constexpr (BF) {
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) split3_bf16(af[rt], ap[rt]);
+    }
+  };
+  float cr[8];
   if constexpr (SH) {
     if (blockIdx.x == 0 && tid == 0) {  // kernels of one stream: no other writer
       cnt[0] += skipped ? 0 : nsh;
@@ -1101,8 +1204,12 @@ __global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
       return;
     }
   }
-  load_c(0, cr);
-  store_c(0, cr);
+  if constexpr (CD) {
+    dma_c(0, 0);
+  } else {
+    load_c(0, cr);
+    store_c(0, cr);
+  }
   if (SH && nsh > 0) {
     load_s(0, anext);
     take_s(anext, af);
@@ -1111,26 +1218,49 @@ __global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
     round_a(anext, af);
     if constexpr (SH) store_s(0, af);
   }
+  split_a();
   __syncthreads();
+  // (A piece, B piece) of the six products, small ones first
+  constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
   for (int ch = 0; ch < nch; ++ch) {
-    load_c(ch + 1, cr);  // unconditional, clamped (see k_gram44)
+    // (the DMA lands before the barrier below, which hipcc closes with vmcnt(0); none behind the
+    // last chunk: the epilogue's tiles take over the buffers)
+    if constexpr (CD) {
+      if (ch + 1 < nch) dma_c((ch + 1) & 1, ch + 1);
+    } else {
+      load_c(ch + 1, cr);  // unconditional, clamped (see k_gram44)
+    }
     // the chunk ahead comes from the shadow or, fresh, from the fp64 basis (uniform; the shadow
     // panels are the leading ones, so the k order is the ascending one either way)
     const bool ns = SH && ch + 1 < nsh;
     if (ns) load_s(ch + 1, anext);
     else load_a(ch + 1, anext);
-    const float* cb = cs[ch & 1] + 2 * q * CLD + 4 * c16;
+    if constexpr (BF) {
+      const float* cb = cs[ch & 1] + (64 * q + c16) * 4;
 #pragma unroll
-    for (int hv = 0; hv < 2 * NH; ++hv) {
-      const int h = hv >> 1, v = hv & 1;
-      const f4v32 bv = *reinterpret_cast<const f4v32*>(cb + (8 * h + v) * CLD);
+      for (int c = 0; c < CT; ++c) {
+        bf8v bp[3];
 #pragma unroll
-      for (int rt = 0; rt < 2; ++rt)
+        for (int p = 0; p < 3; ++p) bp[p] = *reinterpret_cast<const bf8v*>(cb + p * CPC + 64 * c);
 #pragma unroll
-        for (int c = 0; c < CT; ++c)
-          acc[rt][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[rt][h][v], bv[c], acc[rt][c], 0, 0, 0);
+        for (int s = 0; s < 6; ++s)
+#pragma unroll
+          for (int rt = 0; rt < 2; ++rt)
+            acc[rt][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[rt][PA[s]], bp[PB[s]], acc[rt][c], 0, 0, 0);
+      }
+    } else {
+      const float* cb = cs[ch & 1] + 2 * q * CLD + 4 * c16;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const f4v32 bv = *reinterpret_cast<const f4v32*>(cb + (8 * (j >> 1) + (j & 1)) * CLD);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+          for (int c = 0; c < CT; ++c)
+            acc[rt][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[rt][j], bv[c], acc[rt][c], 0, 0, 0);
+      }
     }
-    store_c((ch + 1) & 1, cr);
+    if constexpr (!CD) store_c((ch + 1) & 1, cr);
     if (ns) {
       take_s(anext, af);
     } else {
@@ -1138,6 +1268,7 @@ __global__ __launch_bounds__(256) void k_tsmm44x32(int64_t nrows, PanelRun X,
       if constexpr (SH)
         if (ch + 1 < nch) store_s(ch + 1, af);
     }
+    split_a();
     __syncthreads();
   }
   // epilogue: D (lane: rows 4 q + v, column c16 of tile c) -> LDS (free after the loop's last
@@ -1179,21 +1310,34 @@ bool tsmm44x32_ok(int64_t nrows, const PanelRun& X, const Panels& Y) {
   return true;
 }
 
+int64_t tsmm44x32_cpieces(int K) { return (int64_t)(K / 32) * kU32CpChunk; }
+
+// (with RBL_U32_CDMA) the C image first; it is skipped with the update
+static void upd32_split_c(const PanelRun& X, const double* C, int ldc, const int* skip, unsigned short* Cp,
+                          hipStream_t st) {
+  constexpr bool kSplit = bool(RBL_U32_BF16) && bool(RBL_U32_CDMA);
+  if (kSplit)
+    hipLaunchKernelGGL(k_upd32_split_c, dim3((unsigned)X.count), dim3(256), 0, st, C, ldc, Cp, skip);
+}
+
 void tsmm44x32(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
-               const int* skip, hipStream_t st) {
+               const int* skip, unsigned short* Cp, hipStream_t st) {
   const int64_t wgs = (nrows + 4 * kU32Rows - 1) / (4 * kU32Rows);
+  upd32_split_c(X, C, ldc, skip, Cp, st);
   hipLaunchKernelGGL(k_tsmm44x32<false>, dim3((unsigned)wgs), dim3(256), 0, st, nrows, X, C, ldc,
-                     const_cast<double*>(Y.ptr[0]), const_cast<double*>(Y.ptr[1]), skip, nullptr, 0, nullptr);
+                     const_cast<double*>(Y.ptr[0]), const_cast<double*>(Y.ptr[1]), skip, nullptr, 0, nullptr,
+                     Cp);
 }
 
 int64_t tsmm44x32_shadow_slot(int64_t nrows) { return shadow_slot_floats(nrows); }
 
 void tsmm44x32_shadow(int64_t nrows, const PanelRun& X, const double* C, int ldc, const Panels& Y,
-                      const int* skip, float* S, int nsh, int* cnt, hipStream_t st) {
+                      const int* skip, float* S, int nsh, int* cnt, unsigned short* Cp, hipStream_t st) {
   const int64_t wgs = (nrows + 4 * kU32Rows - 1) / (4 * kU32Rows);
+  upd32_split_c(X, C, ldc, skip, Cp, st);
   hipLaunchKernelGGL(k_tsmm44x32<true>, dim3((unsigned)wgs), dim3(256), 0, st, nrows, X, C, ldc,
                      const_cast<double*>(Y.ptr[0]), const_cast<double*>(Y.ptr[1]), skip, S,
-                     std::min(std::max(nsh, 0), X.count), cnt);
+                     std::min(std::max(nsh, 0), X.count), cnt, Cp);
 }
 
 void shadow_block_rowmajor(const float* slot, int64_t nrows, float* out) {

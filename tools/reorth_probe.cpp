@@ -1,5 +1,5 @@
 // reorth_probe.cpp — time the shipped partial-reorth kernels (gram44_partial + reduce_slab,
-// tsmm44, and at b = 32 the fp32-MFMA update tsmm44x32 of RBL_OPT_UPD32 beside it, plain and in
+// tsmm44, and at b = 32 the fp32 update tsmm44x32 of RBL_OPT_UPD32 (bf16 MFMA) beside it, plain and in
 // its RBL_OPT_UPD32_SHADOW form as a run calls it: the last two panels fresh, the others from the
 // fp32 shadow) at n = 1e7, b = 32, X = [Q_i, Q_{i-1}] for a range of basis sizes (diagnostic).
 // Build: tools/build_probe.sh (links the library's objects).
@@ -48,6 +48,8 @@ int main(int argc, char** argv) {
   int* cnt = nullptr;
   if (b == 32 && hipMalloc(&S, (size_t)rbl::tsmm44x32_shadow_slot(n) * nWmax * 4) != hipSuccess) return 1;
   if (hipMalloc(&cnt, 2 * sizeof(int)) != hipSuccess) return 1;
+  unsigned short* Cp = nullptr;  // the update's split image of C
+  if (b == 32 && hipMalloc(&Cp, (size_t)rbl::tsmm44x32_cpieces(nWmax * b) * 2) != hipSuccess) return 1;
   (void)hipMemset(cnt, 0, 2 * sizeof(int));
   // PROBE_XG=1: the update also forms Q_{i-1}^T Q_i (the fused local-reorth Gram)
   const bool xg = getenv("PROBE_XG") && atoi(getenv("PROBE_XG"));
@@ -84,11 +86,11 @@ int main(int argc, char** argv) {
       (void)hipEventRecord(e1);
       rbl::tsmm44(n, Wr, C, xw, X, -1.0, 1.0, nullptr, 0, xg ? xslab : nullptr, &xgrid);
       (void)hipEventRecord(e2);
-      if (u32) rbl::tsmm44x32(n, Wr, C, xw, X, nullptr, 0);  // the same update on fp32 MFMA
+      if (u32) rbl::tsmm44x32(n, Wr, C, xw, X, nullptr, Cp, 0);  // the same update in fp32 on bf16 MFMA
       (void)hipEventRecord(e3);
       // the shadow form of a run's even step: panels 0 .. nW - 3 were stored by the earlier sizes
       // of this loop (W never changes here), the last two are fresh
-      if (u32 && Wr.stride) rbl::tsmm44x32_shadow(n, Wr, C, xw, X, nullptr, S, nW - 2, cnt, 0);
+      if (u32 && Wr.stride) rbl::tsmm44x32_shadow(n, Wr, C, xw, X, nullptr, S, nW - 2, cnt, Cp, 0);
       (void)hipEventRecord(e4);
       (void)hipEventSynchronize(e4);
       float g, t, u, sh;
@@ -126,7 +128,7 @@ int main(int argc, char** argv) {
   printf("sum over nW=2..%d step 2: gram %.1f ms (%.1f TF, %.2f TB/s)  tsmm %.1f ms (%.1f TF, %.2f TB/s)\n", nWmax,
          tg, fl / tg / 1e9, byg / tg / 1e9, tt, fl / tt / 1e9, byt / tt / 1e9);
   if (tu > 0)
-    printf("                        upd32 (fp32 MFMA) %.1f ms (%.1f TF, %.2f TB/s)\n", tu, fl / tu / 1e9, byt / tu / 1e9);
+    printf("                        upd32 (fp32 sums, bf16 MFMA) %.1f ms (%.1f TF, %.2f TB/s)\n", tu, fl / tu / 1e9, byt / tu / 1e9);
   if (ts > 0)
     printf("                        upd32 with the fp32 shadow %.1f ms (%.1f TF, %.2f TB/s of its own bytes)\n", ts,
            fl / ts / 1e9, bys / ts / 1e9);
