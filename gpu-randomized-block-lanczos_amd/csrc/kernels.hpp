@@ -471,6 +471,17 @@ int kernop_cross_splits(int64_t mr, int64_t mc, int d4);
 bool kernop_cross(const KernCross& op, const double* W, int b, double* Y, double* part, int splits,
                   hipStream_t s);
 
+// --- kernelop_hadamard.hip: kernel-matrix derivative products (rbl_kernel_hadamard) ---------------
+// U = (Phi o A B^T) Q over the points of op (its scale and nugget do not enter): Phi_ij = kappa or one
+// of its derivatives (the values of RBL_KWEIGHT_*; kernelop_dev.hpp phi), Ap and Bp the n x r factors
+// row-major and zero-padded to r4 = 4 ceil(r / 4) columns, Q and U n x b row-major with leading
+// dimension b (U must not alias Q).  d4 + r4 <= kKernMaxDim.  Any b >= 1 on fp64 MFMA, one launch
+// per column chunk, grid ceil(n / 64), the column range not split; fixed summation order, no atomics,
+// no scratch.  false: bad shape or mode (nothing launched).
+constexpr int kKernWeightValue = 0, kKernWeightDgamma = 1, kKernWeightDscale = 2;
+bool kernop_hadamard(const KernOp& op, int mode, int r4, const double* Ap, const double* Bp, const double* Q,
+                     int b, double* U, hipStream_t s);
+
 // --- tsmm.hip ----------------------------------------------------------------------------
 // Partial Gram: slab[s][a][c] = sum over rows of split s of W[r][a] * X[r][c]
 //   W: run of nW panels (a in [0, nW*w)), X: panels (c in [0, X.count*X.w)).

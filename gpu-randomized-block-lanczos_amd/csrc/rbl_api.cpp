@@ -3673,6 +3673,116 @@ int rbl_bench_kernel_cross(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz
   return RBL_OK;
 }
 
+namespace {
+// The buffers of one derivative product (rbl_kernel_hadamard, rbl_bench_kernel_hadamard): they live
+// as long as the call — the two factors row-major n x r4 (zero-padded columns), the block and the
+// result row-major, and one column-major image for the transposes.
+struct HadamardBufs {
+  DevBuf<double> a, b, q, qr, u;
+};
+static_assert(RBL_KWEIGHT_VALUE == kKernWeightValue && RBL_KWEIGHT_DGAMMA == kKernWeightDgamma &&
+                  RBL_KWEIGHT_DSCALE == kKernWeightDscale,
+              "rbl_hip.h and kernels.hpp name the same weights");
+
+bool hadamard_mode_ok(int mode) {
+  return mode == RBL_KWEIGHT_VALUE || mode == RBL_KWEIGHT_DGAMMA || mode == RBL_KWEIGHT_DSCALE;
+}
+// F (n x r, column-major, ldf) -> row-major n x r4 zero-padded; false at a non-finite entry
+bool hadamard_factor(int64_t n, int r, int r4, const double* F, int64_t ldf, std::vector<double>& fr) {
+  fr.assign((size_t)n * r4, 0.0);
+  for (int k = 0; k < r; ++k)
+    for (int64_t i = 0; i < n; ++i) {
+      const double v = F[i + k * ldf];
+      if (!std::isfinite(v)) return false;
+      fr[(size_t)i * r4 + k] = v;
+    }
+  return true;
+}
+}  // namespace
+
+int rbl_kernel_hadamard(rbl_ctx* ctx, int mode, int r, const double* A, int64_t lda, const double* B, int64_t ldb,
+                        int b, const double* Q, int64_t ldq, double* U, int64_t ldu) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (!ctx->kernop) return fail(ctx, RBL_ERR_STATE, "rbl_kernel_hadamard: no kernel matrix");
+  if (!hadamard_mode_ok(mode)) return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_hadamard: unknown weight mode");
+  const int d4 = ctx->kern_d4;
+  if (r < 1 || r > RBL_KERNOP_MAX_DIM || d4 + 4 * ((r + 3) / 4) > RBL_KERNOP_MAX_DIM)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_hadamard: r must be >= 1 with 4 ceil(d / 4) + 4 ceil(r / 4) <= " +
+                                          std::to_string(RBL_KERNOP_MAX_DIM));
+  if (b < 1 || b > RBL_MAX_BLOCK)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_hadamard: b must be in [1," + std::to_string(RBL_MAX_BLOCK) + "]");
+  const int64_t n = ctx->n;
+  if (!A || !B || !Q || !U || lda < n || ldb < n || ldq < n || ldu < n)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_hadamard: NULL block or a leading dimension below n");
+  const int r4 = 4 * ((r + 3) / 4);
+  std::vector<double> ar, br, qh((size_t)n * b);
+  if (!hadamard_factor(n, r, r4, A, lda, ar) || !hadamard_factor(n, r, r4, B, ldb, br))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_hadamard: A or B has a non-finite entry");
+  for (int c = 0; c < b; ++c)
+    for (int64_t i = 0; i < n; ++i) {
+      const double v = Q[i + c * ldq];
+      if (!std::isfinite(v)) return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_hadamard: Q has a non-finite entry");
+      qh[(size_t)i + (size_t)c * n] = v;
+    }
+  HIPC(hipSetDevice(ctx->device));
+  HadamardBufs H;
+  HIPC(H.a.alloc((size_t)n * r4));
+  HIPC(H.b.alloc((size_t)n * r4));
+  HIPC(H.q.alloc((size_t)n * b));
+  HIPC(H.qr.alloc((size_t)n * b));
+  HIPC(H.u.alloc((size_t)n * b));
+  HIPC(hipMemcpyAsync(H.a, ar.data(), ar.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(H.b, br.data(), br.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(H.q, qh.data(), qh.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  colmajor_to_rowmajor(H.q, n, b, H.qr, ctx->stream);
+  if (!kernop_hadamard(kernop(ctx), mode, r4, H.a, H.b, H.qr, b, H.u, ctx->stream))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_hadamard: shape out of range");
+  HIPC(hipGetLastError());
+  rowmajor_to_colmajor(H.u, n, b, H.q, ctx->stream);
+  HIPC(hipMemcpyAsync(qh.data(), H.q, qh.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (int c = 0; c < b; ++c) std::copy_n(qh.data() + (size_t)c * n, n, U + c * ldu);
+  return RBL_OK;
+}
+
+int rbl_bench_kernel_hadamard(rbl_ctx* ctx, int mode, int r, int b, int reps, double* ms) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (!ctx->kernop) return fail(ctx, RBL_ERR_STATE, "rbl_bench_kernel_hadamard: no kernel matrix");
+  const int d4 = ctx->kern_d4;
+  if (!hadamard_mode_ok(mode) || r < 1 || r > RBL_KERNOP_MAX_DIM || d4 + 4 * ((r + 3) / 4) > RBL_KERNOP_MAX_DIM ||
+      b < 1 || b > RBL_MAX_BLOCK || reps < 1 || !ms)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kernel_hadamard: bad arguments");
+  const int64_t n = ctx->n;
+  const int r4 = 4 * ((r + 3) / 4);
+  HIPC(hipSetDevice(ctx->device));
+  HadamardBufs H;
+  HIPC(H.a.alloc((size_t)n * r4));
+  HIPC(H.b.alloc((size_t)n * r4));
+  HIPC(H.qr.alloc((size_t)n * b));
+  HIPC(H.u.alloc((size_t)n * b));
+  // N(0,1) in every column, the padded ones included: the time does not depend on the values
+  randn_block(H.a, n, r4, 0, 1, ctx->stream);
+  randn_block(H.b, n, r4, 0, 2, ctx->stream);
+  randn_block(H.qr, n, b, 0, 3, ctx->stream);
+  const KernOp op = kernop(ctx);
+  if (!kernop_hadamard(op, mode, r4, H.a, H.b, H.qr, b, H.u, ctx->stream))  // warm-up
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kernel_hadamard: shape out of range");
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  int st = RBL_OK;
+  if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+  for (int k = 0; k < reps; ++k) kernop_hadamard(op, mode, r4, H.a, H.b, H.qr, b, H.u, ctx->stream);
+  if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+  float t = 0.f;
+  if (hipEventElapsedTime(&t, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+  *ms = (double)t / reps;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_kernel_hadamard: a HIP call failed");
+  return RBL_OK;
+}
+
 int rbl_rect_info(rbl_ctx* ctx, int64_t* nrows, int64_t* ncols, int64_t* nnz) {
   if (!ctx) return RBL_ERR_INVALID;
   if (!ctx->rect) return fail(ctx, RBL_ERR_STATE, "rbl_rect_info: no rectangular matrix");

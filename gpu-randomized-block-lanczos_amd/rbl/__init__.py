@@ -16,7 +16,8 @@ diag f(A) by Chebyshev series (``heat_kernel_signature``, ``subgraph_centrality`
 the rows of X as the A of any of these (``RBL_kernel_pca``, ``RBL_spectral_embedding``,
 ``kernel_centering_update``), and ``kernel_pca_fit`` / ``spectral_embedding_fit`` / ``gp_fit`` keep such a
 fit as a model that serves points outside the training set (``transform``, ``predict``) through the
-cross-kernel product ``Context.kernel_cross``; ``solve(A, B, shift=)`` (``rbl.solve``) solves
+cross-kernel product ``Context.kernel_cross``; ``kernel_gradients`` and ``GPModel.mll_gradient`` give
+hyperparameter gradients through the derivative product ``Context.kernel_hadamard``; ``solve(A, B, shift=)`` (``rbl.solve``) solves
 (A + shift I) X = B on any of these operators by batched preconditioned CG
 (``spectral_preconditioner``, ``cg_tridiag``, ``logdet_lanczos``); ``Context`` wraps the C-ABI of
 librbl_hip.so (include/rbl_hip.h).  Importing this package loads the HIP library and fails
@@ -38,9 +39,10 @@ from .density import (RBL_interval, check_moments, eig_count, interval_degree, i
                       jackson, kpm_count, kpm_density, spectral_density)
 from .lowrank import (RBL_modularity, centering_update, deflation_update,  # noqa: F401
                       modularity_update)
-from .kernelop import (GPModel, KernelMatrix, KernelPCAModel, RBL_kernel_pca,  # noqa: F401
-                       RBL_spectral_embedding, SpectralEmbeddingModel, cross_splits, gp_fit,
-                       kernel_centering_update, kernel_pca_fit, row_normalize, spectral_embedding_fit)
+from .kernelop import (GPModel, KernelGradient, KernelMatrix, KernelPCAModel, MLLGradient,  # noqa: F401
+                       RBL_kernel_pca, RBL_spectral_embedding, SpectralEmbeddingModel, cross_splits, gp_fit,
+                       hadamard_max_rank, kernel_centering_update, kernel_gradients, kernel_pca_fit,
+                       row_normalize, scale_gradient_sums, spectral_embedding_fit)
 from .funm import (DiagResult, apply_function, cheb_coeffs, cheb_fit, diag_function, diag_series,  # noqa: F401
                    heat_kernel_signature, local_density, logdet, subgraph_centrality, trace_function)
 from .solve import (SolveInfo, cg_tridiag, lanczos_quadrature, logdet_lanczos, solve,  # noqa: F401

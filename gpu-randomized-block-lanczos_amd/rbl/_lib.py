@@ -68,6 +68,10 @@ RBL_KERNEL_POLY = 2
 RBL_KERNOP_MAX_DIM = 256
 RBL_SPMM_KERNEL_KERNOP = 9
 RBL_MATRIX_FORMAT_KERNOP = 6
+# rbl_kernel_hadamard: the weight Phi (kappa, d kappa / d gamma, the factor of d kappa / d log s_k)
+RBL_KWEIGHT_VALUE = 0
+RBL_KWEIGHT_DGAMMA = 1
+RBL_KWEIGHT_DSCALE = 2
 # rbl_cheb_diag: the block drawn when X is NULL
 RBL_PROBE_GAUSS = 0
 RBL_PROBE_SIGN = 1
@@ -123,6 +127,8 @@ SIGNATURES = {
     "rbl_kernel_cross": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, _pd, _i64, _pd, _i64]),
     "rbl_kernel_cross_splits": (C.c_int, [_i64, _i64, C.c_int]),
     "rbl_bench_kernel_cross": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _pd]),
+    "rbl_kernel_hadamard": (C.c_int, [_p, C.c_int, C.c_int, _pd, _i64, _pd, _i64, C.c_int, _pd, _i64, _pd, _i64]),
+    "rbl_bench_kernel_hadamard": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _pd]),
     "rbl_gen_matrix_hashwindow": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_circuit": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_rmat": (C.c_int, [_p, _i64, C.c_int, _i64, C.c_double, C.c_double, C.c_double,

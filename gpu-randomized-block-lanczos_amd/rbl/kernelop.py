@@ -31,6 +31,8 @@ from . import _lib
 from .rbl_gpu import Context, lanczos
 
 KINDS = {"rbf": _lib.RBL_KERNEL_RBF, "laplace": _lib.RBL_KERNEL_LAPLACE, "poly": _lib.RBL_KERNEL_POLY}
+# the weight Phi of Context.kernel_hadamard: kappa, d kappa / d gamma, the factor of d kappa / d log s_k
+WEIGHTS = {"value": _lib.RBL_KWEIGHT_VALUE, "dgamma": _lib.RBL_KWEIGHT_DGAMMA, "dscale": _lib.RBL_KWEIGHT_DSCALE}
 
 
 def _new_points(what, Z, d):
@@ -454,6 +456,175 @@ class GPModel(_KernelFit):
                                 seed, None)
         fit = float(np.sum(self.y * self.alpha))
         return -0.5 * fit - 0.5 * t * ld - 0.5 * n * t * np.log(2.0 * np.pi), 0.5 * t * err
+
+
+    def mll_gradient(self, nvec: int = 32, seed: int = 0, ard: bool = False, probes=None) -> "MLLGradient":
+        """The gradient of log p(y | X) (summed over the t columns of y) with respect to log gamma, log
+        noise and, with ard, the logarithms of per-coordinate length scales s_k at s = 1 (the kernel on
+        the points x o s).  For any kernel parameter theta
+
+            dL / d theta = sum_ij M_ij dK_ij / d theta,    M = 1/2 alpha alpha^T - t/2 (K + noise I)^-1,
+
+        and with nvec probes z_c (E z z^T = I) and w_c = (K + noise I)^-1 z_c the inverse is replaced by
+        the symmetric low-rank estimate (1 / 2 nv) sum_c (w_c z_c^T + z_c w_c^T), so M ~ A B^T with
+        A = [alpha / 2, -t W / (4 nv), -t Z / (4 nv)], B = [alpha, Z, W]; ``kernel_gradients`` then needs
+        one derivative product of width 1 (gamma) and one of width d + 1 (the scales), K never formed.
+        Z: Rademacher probes drawn on the host from ``seed`` (``rbl.solve.rademacher``, as
+        ``logdet_lanczos``), or ``probes`` (n x nv) in their place — probes = sqrt(n) I makes the trace
+        term exact.  W comes from the fit's CG (tol, max_iter, preconditioner): only a model fitted with
+        solver="cg" has one, any other raises ValueError.  dlog_noise = noise (1/2 |alpha|^2 - t / (2 nv)
+        sum_c z_c . w_c).
+
+        ``stderr`` holds the standard error over the probes of the trace part of each component, from
+        per-probe contributions tau_c = w_c^T (dK / d theta) z_c: they come from further products
+        Phi [Z, x_k o Z, x_k^2 o Z] with A = B = 1 (nv columns, and 2 d nv more with ard), not from the
+        low-rank launch, which only yields their sum.  The data-fit part is exact to the solver's tol.
+
+        The laplace kernel is not differentiable at coincident points: pairs whose Gram-form squared
+        distance is rounding noise contribute up to about gamma sqrt(N_ij u) each to ``dlog_scales``
+        (N_ij = |x_i|^2 + |x_j|^2, u = 2^-53).  The other components are well conditioned."""
+        if self.solver != "cg":
+            raise ValueError('GPModel.mll_gradient: only for a model fitted with solver="cg" (the probes are '
+                             "solved by the fit's CG)")
+        from .solve import rademacher
+        n, t = self.y.shape
+        if probes is None:
+            if isinstance(nvec, bool) or not isinstance(nvec, (int, np.integer)) or nvec < 2:
+                raise ValueError("GPModel.mll_gradient: nvec must be an integer >= 2")
+            Z = rademacher(n, int(nvec), seed)
+        else:
+            Z = np.asarray(probes, dtype=np.float64)
+            if Z.ndim != 2 or Z.shape[0] != n or Z.shape[1] < 2 or not np.all(np.isfinite(Z)):
+                raise ValueError(f"GPModel.mll_gradient: probes must be a finite n x nv array, n = {n}, nv >= 2")
+        nv = Z.shape[1]
+        K = self.K
+        with Context(self.device) as ctx:
+            ctx.set_matrix(K)
+            if self.precond is not None:
+                ctx.set_preconditioner(*self.precond)
+            W = self._cg_solve(ctx, Z)
+            A = np.column_stack([0.5 * self.alpha, (-0.25 * t / nv) * W, (-0.25 * t / nv) * Z])
+            B = np.column_stack([self.alpha, Z, W])
+            g = kernel_gradients(ctx, A, B, ard=ard, X=K.X)
+            tau_g, tau_s = _probe_contributions(ctx, K, Z, W, ard)
+        zw = (Z * W).sum(axis=0)
+        half = 0.5 * t / np.sqrt(nv)
+        err = {"dlog_gamma": half * K.gamma * float(np.std(tau_g, ddof=1)),
+               "dlog_noise": half * K.nugget * float(np.std(zw, ddof=1)),
+               "dlog_scales": half * np.std(tau_s, axis=0, ddof=1) if ard else None}
+        return MLLGradient(g.dlog_gamma, K.nugget * g.trace, g.dlog_scales, err)
+
+
+class KernelGradient:
+    """``kernel_gradients``: dlog_gamma = sum_ij (A B^T)_ij dK_ij / d log gamma, dlog_scales the same
+    for the d per-coordinate log length scales (None without ard), trace = sum_i a_i . b_i, the
+    coefficient of d / d noise."""
+
+    def __init__(self, dlog_gamma, dlog_scales, trace):
+        self.dlog_gamma, self.dlog_scales, self.trace = dlog_gamma, dlog_scales, trace
+
+
+class MLLGradient:
+    """``GPModel.mll_gradient``: dlog_gamma, dlog_noise, dlog_scales (length d, or None) and ``stderr``,
+    a dict of the standard error of each by those names."""
+
+    def __init__(self, dlog_gamma, dlog_noise, dlog_scales, stderr):
+        self.dlog_gamma, self.dlog_noise, self.dlog_scales, self.stderr = dlog_gamma, dlog_noise, dlog_scales, stderr
+
+
+def hadamard_max_rank(d: int) -> int:
+    """The most columns of A and B one ``Context.kernel_hadamard`` launch takes for points in d
+    dimensions: 4 ceil(d / 4) + 4 ceil(r / 4) <= 256."""
+    return _lib.RBL_KERNOP_MAX_DIM - 4 * ((int(d) + 3) // 4)
+
+
+def scale_gradient_sums(kind: str, X, U) -> np.ndarray:
+    """The host half of the per-coordinate gradients: g_k from U = (Psi o A B^T) [X, 1] (n x (d + 1)),
+    Psi the "dscale" weight and A B^T symmetric.  Radial kernels: d kappa / d log s_k = psi (x_ik -
+    x_jk)^2, so g_k = 2 sum_i x_ik^2 U_id - 2 sum_i x_ik U_ik; poly: psi x_ik x_jk, g_k = sum_i x_ik U_ik."""
+    X, U = np.asarray(X, dtype=np.float64), np.asarray(U, dtype=np.float64)
+    d = X.shape[1]
+    if kind == "poly":
+        return (X * U[:, :d]).sum(axis=0)
+    return 2.0 * ((X * X) * U[:, d:d + 1]).sum(axis=0) - 2.0 * (X * U[:, :d]).sum(axis=0)
+
+
+def kernel_gradients(ctx_or_K, A, B, *, ard: bool = False, X=None, device: int = 0) -> KernelGradient:
+    """sum_ij (A B^T)_ij dK_ij / d theta for theta = log gamma and, with ard, theta = log s_k, the
+    per-coordinate length scales of the kernel on the points x o s at s = 1 — the gradient of any
+    objective whose derivative with respect to K is the low-rank matrix A B^T (n x r factors): the GP
+    log marginal likelihood (``GPModel.mll_gradient``), kernel alignment, kernel-PCA objectives.
+    A B^T MUST BE SYMMETRIC; this is not checked (the per-coordinate sums use it).
+
+    ``ctx_or_K``: a KernelMatrix (a context is made on ``device``), or a Context holding one — then
+    ``X``, the n x d points it was loaded with, is needed for ard.  K is never formed:
+    dlog_gamma = gamma sum_i ((Phi_dgamma o A B^T) 1)_i from one derivative product of width 1, and
+    with ard one of width d + 1, U = (Psi o A B^T) [X, 1], followed by ``scale_gradient_sums``.  An r
+    beyond ``hadamard_max_rank(d)`` is split into column groups of A and B whose U's are added in
+    group order.  trace = sum_i a_i . b_i."""
+    if isinstance(ctx_or_K, KernelMatrix):
+        with Context(device) as ctx:
+            ctx.set_matrix(ctx_or_K)
+            return kernel_gradients(ctx, A, B, ard=ard, X=ctx_or_K.X)
+    ctx = ctx_or_K
+    info = ctx.kernel_info()
+    n, d = info["n"], info["d"]
+    kind = {v: k for k, v in KINDS.items()}[info["kind"]]
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    if A.ndim == 1:
+        A = A.reshape(-1, 1)
+    if B.ndim == 1:
+        B = B.reshape(-1, 1)
+    if A.ndim != 2 or A.shape != B.shape or A.shape[0] != n or A.shape[1] < 1:
+        raise ValueError(f"kernel_gradients: A and B must be n x r arrays of one shape, n = {n}")
+    rmax = hadamard_max_rank(d)
+    if rmax < 1:
+        raise ValueError(f"kernel_gradients: d = {d} leaves no room for a factor column (d <= 252)")
+    if ard:
+        if X is None:
+            raise ValueError("kernel_gradients: ard on a Context needs X, the points it was loaded with")
+        X = np.asarray(X, dtype=np.float64)
+        if X.shape != (n, d):
+            raise ValueError(f"kernel_gradients: X must be {n} x {d}")
+
+    def product(Q, weight):
+        U = None
+        for c0 in range(0, A.shape[1], rmax):
+            Ug = ctx.kernel_hadamard(A[:, c0:c0 + rmax], B[:, c0:c0 + rmax], Q, weight)
+            U = Ug if U is None else U + Ug
+        return U
+
+    dlog_gamma = info["gamma"] * float(product(np.ones((n, 1)), "dgamma").sum())
+    dlog_scales = None
+    if ard:
+        dlog_scales = scale_gradient_sums(kind, X, product(np.column_stack([X, np.ones(n)]), "dscale"))
+    return KernelGradient(dlog_gamma, dlog_scales, float(np.sum(A * B)))
+
+
+def _probe_contributions(ctx, K: KernelMatrix, Z, W, ard: bool):
+    """Per probe c: tau_c = w_c^T (dK / d gamma) z_c (nv), and with ard tau_ck = w_c^T (dK / d log s_k)
+    z_c (nv x d), from products Phi Q with A = B = 1 in column chunks of at most RBL_MAX_BLOCK."""
+    n, nv = Z.shape
+    one = np.ones((n, 1))
+
+    def phi_times(Q, weight):
+        return np.column_stack([ctx.kernel_hadamard(one, one, Q[:, c0:c0 + _lib.RBL_MAX_BLOCK], weight)
+                                for c0 in range(0, Q.shape[1], _lib.RBL_MAX_BLOCK)])
+
+    tau_g = (W * phi_times(Z, "dgamma")).sum(axis=0)
+    if not ard:
+        return tau_g, None
+    X = K.X
+    tau_s = np.empty((nv, K.d))
+    P = phi_times(Z, "dscale")
+    for k in range(K.d):
+        xk = X[:, k:k + 1]
+        if K.kind == "poly":
+            tau_s[:, k] = (W * xk * phi_times(xk * Z, "dscale")).sum(axis=0)
+            continue
+        RS = phi_times(np.column_stack([xk * Z, xk * xk * Z]), "dscale")
+        tau_s[:, k] = (W * (xk * xk * P - 2.0 * xk * RS[:, :nv] + RS[:, nv:])).sum(axis=0)
+    return tau_g, tau_s
 
 
 _SOLVE_CHUNK = 64   # columns per rbl_apply_filter call, as rbl.funm.APPLY_CHUNK

@@ -332,6 +332,46 @@ class Context:
                     "rbl_bench_kernel_cross")
         return float(ms[0])
 
+    def kernel_hadamard(self, A, B, Q, weight="value") -> np.ndarray:
+        """U (n x b) = (Phi o A B^T) Q over the points of the kernel matrix held
+        (rbl_kernel_hadamard): A and B n x r, Q n x b, Phi_ij = kappa (weight "value"), d kappa /
+        d gamma ("dgamma") or the factor psi of d kappa / d log s_k ("dscale": times (x_ik - x_jk)^2
+        for the radial kernels, x_ik x_jk for poly), or the RBL_KWEIGHT_* id.  The operator's scale
+        and nugget do not enter.  4 ceil(d / 4) + 4 ceil(r / 4) <= 256.  Two calls give the same bits."""
+        from .kernelop import WEIGHTS
+        if isinstance(weight, str):
+            if weight not in WEIGHTS:
+                raise ValueError("kernel_hadamard: weight must be 'value', 'dgamma' or 'dscale'")
+            weight = WEIGHTS[weight]
+        n = self.kernel_info()["n"]
+        blocks = []
+        for name, M in (("A", A), ("B", B), ("Q", Q)):
+            M = np.asarray(M, dtype=np.float64)
+            if M.ndim == 1:
+                M = M.reshape(-1, 1)
+            if M.ndim != 2 or M.shape[0] != n or M.shape[1] < 1:
+                raise ValueError(f"kernel_hadamard: {name} must have n = {n} rows and at least one column")
+            if not np.all(np.isfinite(M)):
+                raise ValueError(f"kernel_hadamard: {name} has a non-finite entry")
+            blocks.append(np.asfortranarray(M))
+        A, B, Q = blocks
+        if A.shape[1] != B.shape[1]:
+            raise ValueError("kernel_hadamard: A and B must have the same number of columns")
+        U = np.zeros((n, Q.shape[1]), order="F")
+        self._check(lib.rbl_kernel_hadamard(self._h, int(weight), A.shape[1], dptr(A), n, dptr(B), n, Q.shape[1],
+                                            dptr(Q), n, dptr(U), n), "rbl_kernel_hadamard")
+        return U
+
+    def bench_kernel_hadamard(self, r: int, b: int, weight="value", reps: int = 5) -> float:
+        """Milliseconds per derivative product of the matrix held with device-resident factors of r
+        columns and a block of b columns (rbl_bench_kernel_hadamard)."""
+        from .kernelop import WEIGHTS
+        ms = np.zeros(1)
+        mode = WEIGHTS[weight] if isinstance(weight, str) else int(weight)
+        self._check(lib.rbl_bench_kernel_hadamard(self._h, mode, int(r), int(b), int(reps), dptr(ms)),
+                    "rbl_bench_kernel_hadamard")
+        return float(ms[0])
+
     # -- implicit symmetric low-rank update: the operator A + P S P^T ------------------------
     def set_lowrank(self, P, S) -> None:
         """The operator becomes A + P S P^T (rbl_set_lowrank): P n x r, S r x r symmetric,

@@ -400,6 +400,36 @@ int rbl_kernel_cross_splits(int64_t rows, int64_t cols, int d);
  * (RBL_ERR_INVALID beyond 64 or the stages of the column range). */
 int rbl_bench_kernel_cross(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int trans, int b,
                            int splits, int reps, double* ms);
+/* Kernel-matrix derivative product over the points of the kernel matrix held:
+ *     U (n x b) = (Phi o A B^T) Q,    Phi_ij = phi(x_i, x_j),    (A B^T)_ij = sum_k A_ik B_jk,
+ * A and B n x r, Q n x b, host column-major blocks like rbl_kernel_cross (lda, ldb, ldq, ldu >= n).
+ * With d2 the Gram-form squared distance of the operator (0 on the diagonal), t = gamma x_i^T x_j +
+ * coef0 and q = degree, phi is
+ *   RBL_KWEIGHT_VALUE   kappa
+ *   RBL_KWEIGHT_DGAMMA  d kappa / d gamma:  rbf -d2 kappa, laplace -sqrt(d2) kappa, poly q x_i^T x_j t^(q-1)
+ *   RBL_KWEIGHT_DSCALE  psi with d kappa / d log s_k = psi (x_ik - x_jk)^2 (rbf, laplace) or psi x_ik x_jk
+ *                       (poly) at unit coordinate scales:  rbf -2 gamma kappa, laplace -gamma kappa /
+ *                       sqrt(d2) and 0 where d2 == 0, poly 2 q gamma t^(q-1)
+ * so sum_ij M_ij dK_ij / d theta for a low-rank M = A B^T is a few O(n d) host sums over one product
+ * (theta = gamma: Q = 1; theta = log s_k: Q = [X, 1]).  Neither the scale nor the nugget of the operator
+ * enters; fold a scale into A and B.  Phi o A B^T is never stored: a_i . b_j is one more Gram-form inner
+ * product of the pair-tile scheme, all on fp64 MFMA, one launch per column chunk (32; a last chunk of 17 ..
+ * 31 columns zero-padded to 32, of 1 .. 16 to 16), the column range not split.  Fixed summation order, no atomics: two calls
+ * give the same bits, and with A = B = ones (r = 1), RBL_KWEIGHT_VALUE and b a multiple of 16 the
+ * result has the bits of rbl_apply on the operator without scale and nugget.
+ * RBL_ERR_STATE without a kernel matrix; RBL_ERR_INVALID for an unknown mode, r < 1 or
+ * 4 ceil(d / 4) + 4 ceil(r / 4) > RBL_KERNOP_MAX_DIM, b outside [1, RBL_MAX_BLOCK], a NULL pointer, a
+ * leading dimension below n, or a non-finite entry of A, B or Q — the context unchanged (a following
+ * rbl_apply gives the bits of one before). */
+#define RBL_KWEIGHT_VALUE   0
+#define RBL_KWEIGHT_DGAMMA  1
+#define RBL_KWEIGHT_DSCALE  2
+int rbl_kernel_hadamard(rbl_ctx* ctx, int mode, int r, const double* A, int64_t lda, const double* B,
+                        int64_t ldb, int b, const double* Q, int64_t ldq, double* U, int64_t ldu);
+/* Milliseconds per derivative product of the matrix held with device-resident N(0,1) factors of r
+ * columns and a block of b columns (the device part of rbl_kernel_hadamard alone): one warm-up, then
+ * `reps` products between two hipEvents. */
+int rbl_bench_kernel_hadamard(rbl_ctx* ctx, int mode, int r, int b, int reps, double* ms);
 int rbl_gen_matrix_hashwindow(rbl_ctx* ctx, int64_t n, int64_t halfwidth, double density,
                               uint64_t seed, int nplant, const double* plant);
 /* Device-side generator of the seeded symmetric R-MAT matrix (BASELINE

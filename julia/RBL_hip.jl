@@ -365,6 +365,35 @@ function RBL_gpu_kernel_predict(X::Matrix{Float64}, W::Matrix{Float64}, Z::Matri
     end
 end
 
+# Kernel-matrix derivative product over the points of the kernel matrix a context holds
+# (rbl_kernel_hadamard): U (n x b) = (Phi o A B^T) Q with A, B n x r and Q n x b; weight = :value
+# Phi = kappa, :dgamma d kappa / d gamma, :dscale the factor psi of d kappa / d log s_k (times
+# (x_ik - x_jk)^2 for :rbf and :laplace, x_ik x_jk for :poly).  Neither the scale nor the nugget of the
+# operator enters.  sum_ij (A B^T)_ij dK_ij / d theta is then a few O(n d) sums over U: Q = ones(n, 1)
+# for theta = gamma, Q = [X ones(n)] for the per-coordinate length scales.
+const RBL_KWEIGHT_IDS = Dict(:value => Cint(0), :dgamma => Cint(1), :dscale => Cint(2))
+
+function RBL_gpu_kernel_hadamard(ctx::Ptr{Cvoid}, A::Matrix{Float64}, B::Matrix{Float64}, Q::Matrix{Float64};
+                                 weight::Symbol = :value)
+    haskey(RBL_KWEIGHT_IDS, weight) ||
+        throw(ArgumentError("RBL_gpu_kernel_hadamard: weight must be :value, :dgamma or :dscale"))
+    nref = zeros(Int64, 1)
+    rbl_check(ctx, ccall((:rbl_kernel_info, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Ptr{Int64}, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint},
+                          Ptr{Cint}, Ptr{Float64}),
+                         ctx, nref, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL), "rbl_kernel_info")
+    n = nref[1]
+    size(A) == size(B) && size(A, 1) == n && size(Q, 1) == n ||
+        throw(ArgumentError("RBL_gpu_kernel_hadamard: A and B must be $n x r, Q $n x b"))
+    U = zeros(Float64, n, size(Q, 2))
+    rbl_check(ctx, ccall((:rbl_kernel_hadamard, librbl_hip), Cint,
+                         (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Cint, Ptr{Float64},
+                          Int64, Ptr{Float64}, Int64),
+                         ctx, RBL_KWEIGHT_IDS[weight], Cint(size(A, 2)), A, n, B, n, Cint(size(Q, 2)), Q, n, U, n),
+              "rbl_kernel_hadamard")
+    return U
+end
+
 # (Op + shift I) X = B by batched preconditioned conjugate gradients on the operator a context holds
 # (rbl_solve; with set_lowrank! the updated one): B n x b, every column its own recurrence to
 # |r| <= tol |b| or max_iter iterations.  precond = (V, dv): M^-1 = I + V diag(dv) V^T

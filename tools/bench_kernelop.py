@@ -13,7 +13,8 @@ both numbers.
 
 Writes one JSON document (default profiles/kernelop_bench.json).
 
---cross times the cross-kernel product kappa(Z, X) W (kernelop_cross.hip) instead: see cross()."""
+--cross times the cross-kernel product kappa(Z, X) W (kernelop_cross.hip) instead: see cross();
+--hadamard the derivative product (Phi o A B^T) Q (kernelop_hadamard.hip): see hadamard()."""
 import argparse
 import json
 import os
@@ -102,8 +103,66 @@ def cross(args):
     print("wrote", out)
 
 
+def hadamard(args):
+    """--hadamard: rbl_bench_kernel_hadamard (hipEvents around `--reps` products after one warm-up,
+    device-resident N(0,1) factors and block) for each (n, d, r, b, mode) of --hadamard-shapes
+    (mode 0 value, 1 dgamma, 2 dscale), and rbl_bench_kernel_pass of the symmetric operator at the same
+    n, d and b = 32: the product of the route it replaces, r (d + 1) columns through the operator in
+    chunks of 32.  The variants alternate within a round; medians over `--rounds` rounds; beside them
+    the instruction model (ks + rs + 4 NB) / (ks + 4 NB) of the time relative to the operator's."""
+    if len(args.hadamard_shapes) % 5:
+        raise SystemExit("--hadamard-shapes takes n d r b mode quintuples")
+    shapes = [tuple(args.hadamard_shapes[i:i + 5]) for i in range(0, len(args.hadamard_shapes), 5)]
+
+    import rbl
+
+    doc = {"kernel": "rbf", "gamma": args.gamma, "reps": args.reps, "rounds": args.rounds, "hadamard": []}
+    ctxs = {}
+    try:
+        for n, d, r, b, mode in shapes:
+            if (n, d) not in ctxs:
+                c = rbl.Context(0)
+                c.set_matrix_kernel(points(n, d), "rbf", args.gamma)
+                ctxs[(n, d)] = c
+            ctxs[(n, d)].bench_kernel_hadamard(r, b, mode, 1)     # warm every shape once
+            ctxs[(n, d)].bench_kernel_pass(32, 1)
+        times = {s: [] for s in shapes}
+        sym = {k: [] for k in ctxs}
+        for _ in range(args.rounds):
+            for k, c in ctxs.items():
+                sym[k].append(c.bench_kernel_pass(32, args.reps))
+            for s in shapes:
+                times[s].append(ctxs[s[:2]].bench_kernel_hadamard(s[2], s[3], s[4], args.reps))
+        for n, d, r, b, mode in shapes:
+            ms, ms_sym = statistics.median(times[(n, d, r, b, mode)]), statistics.median(sym[(n, d)])
+            ks, rs, nb = (d + 3) // 4, (r + 3) // 4, 2 if b > 16 else 1
+            # the route through the operator: r b columns; for d kappa / d gamma of the rbf kernel, whose
+            # factor -d2 = -(|x_i|^2 + |x_j|^2 - 2 x_i.x_j) has to be spelled out, r (d + 2) per column of Q
+            cols = r * b * (d + 2 if mode == 1 else 1)
+            row = {"n": n, "d": d, "r": r, "b": b, "mode": mode, "ms": ms, "ms_rounds": times[(n, d, r, b, mode)],
+                   "ms_symmetric_b32": ms_sym, "over_symmetric_b32": ms / ms_sym,
+                   "model_over_symmetric_b32": (ks + rs + 4 * nb) / (ks + 8.0),
+                   "route_columns": cols, "route_ms": cols / 32.0 * ms_sym, "route_over_launch": cols / 32.0 * ms_sym / ms}
+            doc["hadamard"].append(row)
+            print(json.dumps(row), flush=True)
+    finally:
+        for c in ctxs.values():
+            c.close()
+    out = args.out if args.out else os.path.join(ROOT, "profiles", "kernelop_hadamard_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--hadamard", action="store_true",
+                    help="time the derivative product instead (profiles/kernelop_hadamard_bench.json)")
+    ap.add_argument("--hadamard-shapes", type=int, nargs="+",
+                    default=[32768, 16, 33, 17, 2, 32768, 16, 65, 17, 2, 32768, 16, 33, 1, 1, 32768, 16, 65, 1, 1,
+                             32768, 16, 1, 32, 0, 32768, 16, 33, 32, 0, 32768, 16, 240, 17, 2],
+                    help="n d r b mode quintuples of --hadamard")
     ap.add_argument("--cross", action="store_true",
                     help="time the cross-kernel product instead (profiles/kernelop_cross_bench.json)")
     ap.add_argument("--cross-shapes", type=int, nargs="+",
@@ -123,6 +182,8 @@ def main():
     args = ap.parse_args()
     if args.cross:
         return cross(args)
+    if args.hadamard:
+        return hadamard(args)
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "kernelop_bench.json")
     if len(args.shapes) % 3:
