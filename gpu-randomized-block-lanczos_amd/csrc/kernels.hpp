@@ -471,6 +471,34 @@ int kernop_cross_splits(int64_t mr, int64_t mc, int d4);
 bool kernop_cross(const KernCross& op, const double* W, int b, double* Y, double* part, int splits,
                   hipStream_t s);
 
+// --- kernelop_knn.hip: k nearest column points of every row point (rbl_kernel_knn) ----------------
+// R mr x d4 row points and C mc x d4 column points with their norms, as KernCross holds them.  Row i
+// gets the k smallest (d2, j) over the column points j, d2 = max((|r_i|^2 + |c_j|^2) - 2 r_i.c_j, 0)
+// from the cross product's MFMA chain, the smaller index first on equal d2; `self`: R and C are one
+// array (mr == mc) and the pair (i, i) is skipped by index.  1 <= k <= kKernKnnMax, k <= mc (mc - 1
+// with self).
+constexpr int kKernKnnMax = 64;
+struct KernKnn {
+  int64_t mr = 0, mc = 0;
+  int d4 = 0;
+  int k = 0;
+  bool self = false;
+  const double* R = nullptr;
+  const double* rnrm = nullptr;
+  const double* C = nullptr;
+  const double* cnrm = nullptr;
+};
+// idx and d2: mr x k row-major, each row sorted ascending in (d2, j).  splits as kernop_cross
+// (kernop_cross_splits is the rule): with splits > 1, part_idx and part_d2 hold splits x mr x k
+// entries and one thread per row merges the splits' lists.  The answer is unique — it does not depend
+// on splits — and there are no atomics.  false: bad shape (nothing launched).
+bool kernop_knn(const KernKnn& op, int32_t* idx, double* d2, int32_t* part_idx, double* part_d2, int splits,
+                hipStream_t s);
+#ifdef RBL_KNN_COUNT
+// diagnostics build: {pair tiles a wave computed, those on which a lane inserted} since the last reset
+bool kernop_knn_counts(unsigned long long out[2], bool reset);
+#endif
+
 // --- kernelop_hadamard.hip: kernel-matrix derivative products (rbl_kernel_hadamard) ---------------
 // U = (Phi o A B^T) Q over the points of op (its scale and nugget do not enter): Phi_ij = kappa or one
 // of its derivatives (the values of RBL_KWEIGHT_*; kernelop_dev.hpp phi), Ap and Bp the n x r factors

@@ -3674,6 +3674,133 @@ int rbl_bench_kernel_cross(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz
 }
 
 namespace {
+static_assert(RBL_KNN_MAX == kKernKnnMax, "rbl_hip.h and kernels.hpp name the same largest k");
+
+// The buffers of one neighbour search (rbl_kernel_knn, rbl_bench_kernel_knn): they live as long as
+// the call — the new points row-major m x d4 with their norms (cross mode), the lists rows x k
+// row-major, and the splits' lists (empty when S = 1).
+struct KnnBufs {
+  DevBuf<double> z, znrm, d2, part_d2;
+  DevBuf<int32_t> idx, part_idx;
+};
+
+// what both entries check, in one order; on RBL_OK zr holds the row-major points of Z (cross mode)
+// and S the splits to use
+int knn_check(rbl_ctx* ctx, const char* who, int64_t m, const double* Z, int64_t ldz, int k, int splits,
+              std::vector<double>& zr, int& S) {
+  const std::string w(who);
+  if (!ctx->kernop) return fail(ctx, RBL_ERR_STATE, w + ": no kernel matrix");
+  const int64_t n = ctx->n;
+  if (Z ? (m < 1 || ldz < m || m >= ((int64_t)1 << 40) / RBL_MAX_BLOCK) : m != 0)
+    return fail(ctx, RBL_ERR_INVALID, w + ": m must be >= 1 with Z (ldz >= m) and 0 without");
+  if (k < 1 || k > RBL_KNN_MAX || k > (Z ? n : n - 1))
+    return fail(ctx, RBL_ERR_INVALID, w + ": k must be in [1," + std::to_string(RBL_KNN_MAX) +
+                                          "] and at most the column points available");
+  if (n > (int64_t)INT32_MAX - 64) return fail(ctx, RBL_ERR_INVALID, w + ": n too large for int32 indices");
+  const int d4 = ctx->kern_d4;
+  const int64_t rows = Z ? m : n;
+  if (splits < 0 || splits > kKernCrossMaxSplits)   // (beyond the stages: kernop_knn refuses)
+    return fail(ctx, RBL_ERR_INVALID, w + ": splits must be 0 (the rule) or in [1,64]");
+  if (Z && !cross_points(m, ctx->kern_d, d4, Z, ldz, zr))
+    return fail(ctx, RBL_ERR_INVALID, w + ": Z has a non-finite entry");
+  S = splits ? splits : kernop_cross_splits(rows, n, d4);
+  return RBL_OK;
+}
+
+// allocate, upload Z (cross mode) and describe the search
+int knn_setup(rbl_ctx* ctx, int64_t m, bool cross, int k, int S, const std::vector<double>& zr, KnnBufs& B,
+              KernKnn& op) {
+  const int64_t n = ctx->n, rows = cross ? m : n;
+  const int d4 = ctx->kern_d4;
+  HIPC(B.idx.alloc((size_t)rows * k));
+  HIPC(B.d2.alloc((size_t)rows * k));
+  if (S > 1) {
+    HIPC(B.part_idx.alloc((size_t)S * rows * k));
+    HIPC(B.part_d2.alloc((size_t)S * rows * k));
+  }
+  op.mr = rows, op.mc = n, op.d4 = d4, op.k = k, op.self = !cross;
+  op.C = ctx->d_kern_x, op.cnrm = ctx->d_kern_nrm;
+  if (cross) {
+    HIPC(B.z.alloc((size_t)m * d4));
+    HIPC(B.znrm.alloc((size_t)m));
+    HIPC(hipMemcpyAsync(B.z, zr.data(), zr.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    kernop_norms(m, d4, B.z, B.znrm, ctx->stream);
+    op.R = B.z, op.rnrm = B.znrm;
+  } else {
+    op.R = ctx->d_kern_x, op.rnrm = ctx->d_kern_nrm;
+  }
+  return RBL_OK;
+}
+}  // namespace
+
+int rbl_kernel_knn(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int k, int splits, int32_t* idx,
+                   int64_t ldi, double* d2, int64_t ldd) {
+  if (!ctx) return RBL_ERR_INVALID;
+  std::vector<double> zr;
+  int S = 1;
+  CHK(knn_check(ctx, "rbl_kernel_knn", m, Z, ldz, k, splits, zr, S));
+  const int64_t rows = Z ? m : ctx->n;
+  if (!idx || !d2 || ldi < rows || ldd < rows)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_knn: NULL output or a leading dimension below its rows");
+  HIPC(hipSetDevice(ctx->device));
+  KnnBufs B;
+  KernKnn op;
+  CHK(knn_setup(ctx, m, Z != nullptr, k, S, zr, B, op));
+  if (!kernop_knn(op, B.idx, B.d2, B.part_idx, B.part_d2, S, ctx->stream))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_knn: splits beyond the stages of the column range, or n too large");
+  HIPC(hipGetLastError());
+  std::vector<int32_t> ih((size_t)rows * k);
+  std::vector<double> dh((size_t)rows * k);
+  HIPC(hipMemcpyAsync(ih.data(), B.idx, ih.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(dh.data(), B.d2, dh.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (int c = 0; c < k; ++c)   // row-major lists -> the caller's column-major blocks
+    for (int64_t i = 0; i < rows; ++i) {
+      idx[i + c * ldi] = ih[(size_t)i * k + c];
+      d2[i + c * ldd] = dh[(size_t)i * k + c];
+    }
+  return RBL_OK;
+}
+
+int rbl_bench_kernel_knn(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int k, int splits, int reps,
+                         double* ms) {
+  if (!ctx) return RBL_ERR_INVALID;
+  std::vector<double> zr;
+  int S = 1;
+  CHK(knn_check(ctx, "rbl_bench_kernel_knn", m, Z, ldz, k, splits, zr, S));
+  if (reps < 1 || !ms) return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kernel_knn: reps must be >= 1 and ms not NULL");
+  HIPC(hipSetDevice(ctx->device));
+  KnnBufs B;
+  KernKnn op;
+  CHK(knn_setup(ctx, m, Z != nullptr, k, S, zr, B, op));
+  if (!kernop_knn(op, B.idx, B.d2, B.part_idx, B.part_d2, S, ctx->stream))  // warm-up
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kernel_knn: splits beyond the stages of the column range, or n too large");
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  int st = RBL_OK;
+#ifdef RBL_KNN_COUNT
+  unsigned long long cnt[2] = {0, 0};
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess || !kernop_knn_counts(cnt, true)) st = RBL_ERR_HIP;
+#endif
+  if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+  for (int r = 0; r < reps; ++r) kernop_knn(op, B.idx, B.d2, B.part_idx, B.part_d2, S, ctx->stream);
+  if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+  float t = 0.f;
+  if (hipEventElapsedTime(&t, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+  *ms = (double)t / reps;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+#ifdef RBL_KNN_COUNT
+  if (st == RBL_OK && kernop_knn_counts(cnt, false))
+    fprintf(stderr, "rbl_bench_kernel_knn: %llu wave tiles per launch, %llu with an insertion\n",
+            cnt[0] / reps, cnt[1] / reps);
+#endif
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_kernel_knn: a HIP call failed");
+  return RBL_OK;
+}
+
+namespace {
 // The buffers of one derivative product (rbl_kernel_hadamard, rbl_bench_kernel_hadamard): they live
 // as long as the call — the two factors row-major n x r4 (zero-padded columns), the block and the
 // result row-major, and one column-major image for the transposes.

@@ -17,7 +17,10 @@ the rows of X as the A of any of these (``RBL_kernel_pca``, ``RBL_spectral_embed
 ``kernel_centering_update``), and ``kernel_pca_fit`` / ``spectral_embedding_fit`` / ``gp_fit`` keep such a
 fit as a model that serves points outside the training set (``transform``, ``predict``) through the
 cross-kernel product ``Context.kernel_cross``; ``kernel_gradients`` and ``GPModel.mll_gradient`` give
-hyperparameter gradients through the derivative product ``Context.kernel_hadamard``; ``solve(A, B, shift=)`` (``rbl.solve``) solves
+hyperparameter gradients through the derivative product ``Context.kernel_hadamard``; ``knn_graph(X, m)``
+(``rbl.knn``: ``knn_lists``, ``graph_from_knn``) builds the m-nearest-neighbour graph of the points on the
+device (``Context.kernel_knn``) as a sparse A, and ``RBL_spectral_embedding`` / ``spectral_embedding_fit`` take
+``neighbors=m`` to run on it; ``solve(A, B, shift=)`` (``rbl.solve``) solves
 (A + shift I) X = B on any of these operators by batched preconditioned CG
 (``spectral_preconditioner``, ``cg_tridiag``, ``logdet_lanczos``); ``Context`` wraps the C-ABI of
 librbl_hip.so (include/rbl_hip.h).  Importing this package loads the HIP library and fails
@@ -43,6 +46,8 @@ from .kernelop import (GPModel, KernelGradient, KernelMatrix, KernelPCAModel, ML
                        RBL_kernel_pca, RBL_spectral_embedding, SpectralEmbeddingModel, cross_splits, gp_fit,
                        hadamard_max_rank, kernel_centering_update, kernel_gradients, kernel_pca_fit,
                        row_normalize, scale_gradient_sums, spectral_embedding_fit)
+from .knn import (KnnSpectralEmbeddingModel, graph_from_knn, knn_graph, knn_lists,  # noqa: F401
+                  knn_nystrom_algebra, knn_weights, normalized_affinity)
 from .funm import (DiagResult, apply_function, cheb_coeffs, cheb_fit, diag_function, diag_series,  # noqa: F401
                    heat_kernel_signature, local_density, logdet, subgraph_centrality, trace_function)
 from .solve import (SolveInfo, cg_tridiag, lanczos_quadrature, logdet_lanczos, solve,  # noqa: F401

@@ -72,6 +72,8 @@ RBL_MATRIX_FORMAT_KERNOP = 6
 RBL_KWEIGHT_VALUE = 0
 RBL_KWEIGHT_DGAMMA = 1
 RBL_KWEIGHT_DSCALE = 2
+# rbl_kernel_knn: the largest k
+RBL_KNN_MAX = 64
 # rbl_cheb_diag: the block drawn when X is NULL
 RBL_PROBE_GAUSS = 0
 RBL_PROBE_SIGN = 1
@@ -127,6 +129,8 @@ SIGNATURES = {
     "rbl_kernel_cross": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, _pd, _i64, _pd, _i64]),
     "rbl_kernel_cross_splits": (C.c_int, [_i64, _i64, C.c_int]),
     "rbl_bench_kernel_cross": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _pd]),
+    "rbl_kernel_knn": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, _pi32, _i64, _pd, _i64]),
+    "rbl_bench_kernel_knn": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, C.c_int, _pd]),
     "rbl_kernel_hadamard": (C.c_int, [_p, C.c_int, C.c_int, _pd, _i64, _pd, _i64, C.c_int, _pd, _i64, _pd, _i64]),
     "rbl_bench_kernel_hadamard": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _pd]),
     "rbl_gen_matrix_hashwindow": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),

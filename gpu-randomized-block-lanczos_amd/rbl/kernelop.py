@@ -22,6 +22,9 @@ A fit is used on points outside the training set through the cross-kernel matrix
 points against the n stored ones), which ``Context.kernel_cross`` multiplies into a block without
 forming it: ``kernel_pca_fit(...).transform(Z)``, ``spectral_embedding_fit(...).transform(Z)`` (the
 Nystrom extension) and ``gp_fit(...).predict(Z, return_var=True)`` / ``.log_marginal_likelihood()``.
+
+``RBL_spectral_embedding`` and ``spectral_embedding_fit`` take ``neighbors=m`` to run on the
+m-nearest-neighbour graph of the points (``rbl.knn``) through the sparse eigensolver instead.
 """
 from __future__ import annotations
 
@@ -193,12 +196,28 @@ def row_normalize(V) -> np.ndarray:
 
 def RBL_spectral_embedding(X, k: int, b: int, *, kind: str = "rbf", gamma: float = 1.0,
                            coef0: float = 0.0, degree: int = 3, max_blocks=None, omega=None,
-                           seed: int = 0, device: int = 0, return_info: bool = False):
+                           seed: int = 0, device: int = 0, return_info: bool = False, neighbors=None,
+                           mode: str = "union", weight: str = "binary"):
     """The normalised spectral embedding of the n points X (Ng, Jordan & Weiss): the k leading
     eigenpairs of D^-1/2 K D^-1/2 with D = diag(K 1).  The degrees come from one product with the
     ones vector and enter as the operator's scale, so K is never formed.  Returns (lam, V, Y): lam
     descending, V n x k, Y the rows of V normalised to unit length — points of one cluster share a
-    direction, so any clustering of Y's rows (k-means is not part of this library) labels them."""
+    direction, so any clustering of Y's rows (k-means is not part of this library) labels them.
+
+    neighbors=m: the affinity is the m-nearest-neighbour graph of the points instead (``rbl.knn``:
+    one device sweep builds the lists, ``graph_from_knn`` with ``mode`` and ``weight`` the graph A;
+    weight="rbf" uses ``gamma``), and D^-1/2 A D^-1/2, D = diag(A 1), goes to the sparse eigensolver as
+    an ordinary CSR matrix.  ValueError naming the count if a vertex has degree 0 (mode="mutual"
+    leaves isolated vertices); ``kind`` must be a radial kernel.  The same return tuple."""
+    if neighbors is not None:
+        from .knn import knn_affinity
+        K, _, N, _ = knn_affinity("RBL_spectral_embedding", X, neighbors, mode, weight, kind, gamma, device)
+        _check_kb("RBL_spectral_embedding", K.n, k, b)
+        with Context(device) as ctx:
+            ctx.set_matrix(N)
+            lam, V, info = _run(ctx, k, b, max_blocks, omega, seed)
+        Y = row_normalize(V)
+        return (lam, V, Y, info) if return_info else (lam, V, Y)
     K = KernelMatrix(X, kind=kind, gamma=gamma, coef0=coef0, degree=degree)
     _check_kb("RBL_spectral_embedding", K.n, k, b)
     if kind != "poly":
@@ -345,9 +364,25 @@ class SpectralEmbeddingModel(_KernelFit):
 
 def spectral_embedding_fit(X, k: int, b: int, *, kind: str = "rbf", gamma: float = 1.0, coef0: float = 0.0,
                            degree: int = 3, max_blocks=None, omega=None, seed: int = 0, tol: float = FIT_TOL,
-                           device: int = 0) -> SpectralEmbeddingModel:
+                           device: int = 0, neighbors=None, mode: str = "union", weight: str = "binary"):
     """The embedding of ``RBL_spectral_embedding`` kept as a model whose ``transform(Z)`` embeds new
-    points by the Nystrom extension.  ValueError for a degree <= 0 or one of the k eigenvalues == 0."""
+    points by the Nystrom extension.  ValueError for a degree <= 0 or one of the k eigenvalues == 0.
+
+    neighbors=m: the embedding on the m-nearest-neighbour graph (as ``RBL_spectral_embedding`` with
+    neighbors=), kept as a ``rbl.knn.KnnSpectralEmbeddingModel`` whose ``transform(Z)`` takes the m
+    neighbours of each new point among the training points and applies the Nystrom extension
+    restricted to them."""
+    if neighbors is not None:
+        from .knn import KnnSpectralEmbeddingModel, knn_affinity
+        K, shift, N, deg = knn_affinity("spectral_embedding_fit", X, neighbors, mode, weight, kind, gamma, device)
+        _check_kb("spectral_embedding_fit", K.n, k, b)
+        with Context(device) as ctx:
+            ctx.set_matrix(N)
+            lam, V, info = _run(ctx, k, b, max_blocks, omega, seed, tol)
+        if np.any(lam == 0.0):
+            raise ValueError("spectral_embedding_fit: a zero eigenvalue has no Nystrom extension (lower k)")
+        return KnnSpectralEmbeddingModel(K, shift, device, int(neighbors), mode, weight, float(gamma), deg, lam, V,
+                                         info)
     K, shift = _centred_kernel("spectral_embedding_fit", X, kind, gamma, coef0, degree)
     _check_kb("spectral_embedding_fit", K.n, k, b)
     with Context(device) as ctx:

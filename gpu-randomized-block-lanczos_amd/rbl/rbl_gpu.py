@@ -332,6 +332,38 @@ class Context:
                     "rbl_bench_kernel_cross")
         return float(ms[0])
 
+    def _knn_args(self, what, k, Z):
+        """(Z as an F-ordered m x d block or None, m, ldz, rows) for the two neighbour entries."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"{what}: k must be an integer")
+        if Z is None:
+            return None, 0, 0, self.kernel_info()["n"]
+        Z, _ = self._cross_points(what, Z)
+        return Z, Z.shape[0], Z.shape[0], Z.shape[0]
+
+    def kernel_knn(self, k: int, Z=None, splits: int = 0):
+        """The k nearest neighbours among the points X of the kernel matrix held (rbl_kernel_knn):
+        of the n points themselves (Z None; the pair (i, i) is skipped by index, k <= n - 1) or of the
+        m new points Z (m x d; no pair skipped, k <= n).  Returns (idx, d2), int32 and float64 arrays
+        rows x k: column c holds the (c + 1)-th nearest point's index in X and its squared Euclidean
+        distance in the operator's Gram form; each row ascending in (d2, index), the smaller index
+        first on equal distances.  The kernel kind, gamma, scale and nugget do not enter.  splits = 0:
+        the library's rule; the result does not depend on it.  Two calls give the same bits."""
+        Z, m, ldz, rows = self._knn_args("kernel_knn", k, Z)
+        idx = np.zeros((rows, max(int(k), 0)), dtype=np.int32, order="F")
+        d2 = np.zeros((rows, max(int(k), 0)), order="F")
+        self._check(lib.rbl_kernel_knn(self._h, m, dptr(Z), ldz, int(k), int(splits),
+                                       idx.ctypes.data_as(_lib._pi32), rows, dptr(d2), rows), "rbl_kernel_knn")
+        return idx, d2
+
+    def bench_kernel_knn(self, k: int, Z=None, splits: int = 0, reps: int = 5) -> float:
+        """Milliseconds per neighbour search of ``kernel_knn`` on the device (rbl_bench_kernel_knn)."""
+        Z, m, ldz, _ = self._knn_args("bench_kernel_knn", k, Z)
+        ms = np.zeros(1)
+        self._check(lib.rbl_bench_kernel_knn(self._h, m, dptr(Z), ldz, int(k), int(splits), int(reps), dptr(ms)),
+                    "rbl_bench_kernel_knn")
+        return float(ms[0])
+
     def kernel_hadamard(self, A, B, Q, weight="value") -> np.ndarray:
         """U (n x b) = (Phi o A B^T) Q over the points of the kernel matrix held
         (rbl_kernel_hadamard): A and B n x r, Q n x b, Phi_ij = kappa (weight "value"), d kappa /

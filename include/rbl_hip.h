@@ -400,6 +400,35 @@ int rbl_kernel_cross_splits(int64_t rows, int64_t cols, int d);
  * (RBL_ERR_INVALID beyond 64 or the stages of the column range). */
 int rbl_bench_kernel_cross(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int trans, int b,
                            int splits, int reps, double* ms);
+/* The k nearest neighbours among the points X (n x d) of the kernel matrix held — the step that turns
+ * points into a sparse k-nearest-neighbour graph for the sparse eigensolver:
+ *   Z == NULL (m must be 0):  the neighbours of the n points among themselves, the pair (i, i) skipped
+ *                             by index (a duplicate point with another index is a neighbour at 0);
+ *                             rows = n, k <= n - 1
+ *   Z != NULL:                the neighbours in X of the m points Z (m x d, column-major, ldz >= m), no
+ *                             pair skipped; rows = m, k <= n
+ * idx (int32) and d2 are rows x k host blocks, column-major, ldi, ldd >= rows: column c holds the
+ * (c + 1)-th nearest and its squared distance.  The distance is always Euclidean — the kernel kind,
+ * gamma, scale and nugget do not enter — in the Gram form of the operator, d2 = max((|x_i|^2 + |x_j|^2)
+ * - 2 x_i.x_j, 0) on fp64 MFMA, so with Z == NULL d2(i, j) and d2(j, i) are the same bits.  Row i's
+ * result is the k smallest under the total order (d2, j), the smaller index first on equal d2, written
+ * ascending: it is unique, so it depends on neither the split count nor the CU count, two calls give
+ * the same bits, and there are no atomics.  splits = 0: the column range is split by
+ * rbl_kernel_cross_splits(rows, n, d); otherwise that many splits, 1 .. 64 and at most the stages of
+ * the column range (64 points for d <= 16, 32 for d <= 64, else 16).  Runs on the context's stream (a
+ * run in flight is waited for); extra device memory for the call only: the points of Z, the lists and
+ * splits x rows x k entries of partial lists.
+ * RBL_ERR_STATE without a kernel matrix; RBL_ERR_INVALID for k < 1, k > RBL_KNN_MAX, k beyond the
+ * column points available, m < 1 with Z, m != 0 without, a NULL output, a leading dimension below its
+ * block's rows, a non-finite entry of Z, or a bad splits — the context unchanged (a following rbl_apply
+ * gives the bits of one before). */
+#define RBL_KNN_MAX 64
+int rbl_kernel_knn(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int k, int splits,
+                   int32_t* idx, int64_t ldi, double* d2, int64_t ldd);
+/* Milliseconds per neighbour search (the device part of rbl_kernel_knn alone, arguments as there):
+ * one warm-up, then `reps` searches between two hipEvents. */
+int rbl_bench_kernel_knn(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int k, int splits,
+                         int reps, double* ms);
 /* Kernel-matrix derivative product over the points of the kernel matrix held:
  *     U (n x b) = (Phi o A B^T) Q,    Phi_ij = phi(x_i, x_j),    (A B^T)_ij = sum_k A_ik B_jk,
  * A and B n x r, Q n x b, host column-major blocks like rbl_kernel_cross (lda, ldb, ldq, ldu >= n).

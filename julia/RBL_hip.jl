@@ -365,6 +365,33 @@ function RBL_gpu_kernel_predict(X::Matrix{Float64}, W::Matrix{Float64}, Z::Matri
     end
 end
 
+# The k nearest neighbours of the rows of X (n x d) among the other rows (Z = nothing: the pair (i, i)
+# is skipped, k <= n - 1), or of the rows of Z (m x d) among the rows of X (k <= n) (rbl_kernel_knn).
+# Returns (idx, d2), rows x k: column c holds the index in X (1-based) of the c-th nearest point and
+# its squared Euclidean distance; every row ascending in (d2, index), the smaller index first on equal
+# distances, so the answer is unique.  sparse(repeat(1:n, k), vec(idx), 1.0, n, n) is the directed
+# k-nearest-neighbour graph; max.(G, G') its symmetric union for RBL_gpu.  One context:
+# set_matrix!(::KernelPoints), rbl_kernel_knn, free.  Centre X (and move Z alike) first: the distance
+# is taken in Gram form.
+function RBL_gpu_knn(X::Matrix{Float64}, k::Int; Z = nothing, device::Int = 0)
+    ctx = rbl_context(device)
+    try
+        set_matrix!(ctx, KernelPoints(X, :rbf, 1.0, 0.0, 3, nothing, 0.0))
+        m = Z === nothing ? 0 : size(Z, 1)
+        rows = Z === nothing ? size(X, 1) : m
+        idx = zeros(Int32, rows, k)
+        d2 = zeros(Float64, rows, k)
+        rbl_check(ctx, ccall((:rbl_kernel_knn, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Cint, Cint, Ptr{Int32}, Int64, Ptr{Float64},
+                              Int64),
+                             ctx, m, Z === nothing ? C_NULL : Z, m, Cint(k), Cint(0), idx, rows, d2, rows),
+                  "rbl_kernel_knn")
+        return idx .+ Int32(1), d2
+    finally
+        ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
+    end
+end
+
 # Kernel-matrix derivative product over the points of the kernel matrix a context holds
 # (rbl_kernel_hadamard): U (n x b) = (Phi o A B^T) Q with A, B n x r and Q n x b; weight = :value
 # Phi = kappa, :dgamma d kappa / d gamma, :dscale the factor psi of d kappa / d log s_k (times

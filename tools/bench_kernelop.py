@@ -14,7 +14,8 @@ both numbers.
 Writes one JSON document (default profiles/kernelop_bench.json).
 
 --cross times the cross-kernel product kappa(Z, X) W (kernelop_cross.hip) instead: see cross();
---hadamard the derivative product (Phi o A B^T) Q (kernelop_hadamard.hip): see hadamard()."""
+--hadamard the derivative product (Phi o A B^T) Q (kernelop_hadamard.hip): see hadamard();
+--knn the k-nearest-neighbour search (kernelop_knn.hip): see knn()."""
 import argparse
 import json
 import os
@@ -155,8 +156,56 @@ def hadamard(args):
     print("wrote", out)
 
 
+def knn(args):
+    """--knn: rbl_bench_kernel_knn (hipEvents around `--reps` searches after one warm-up) for each
+    (n, d, k) of --knn-shapes, the neighbours of the n points among themselves with the library's
+    split, and rbl_bench_kernel_pass of the symmetric operator over the same points at b = 32 — the
+    product whose first MFMA chain the search shares.  The two alternate within a round; medians over
+    `--rounds` rounds; beside them the estimate k (1 + ln(n / k)) of a row's insertions.  A library
+    built with -DRBL_KNN_COUNT (tools/build_variant.sh, RBL_LIB=) prints the share of wave tiles with
+    an insertion to stderr."""
+    if len(args.knn_shapes) % 3:
+        raise SystemExit("--knn-shapes takes n d k triples")
+    shapes = [tuple(args.knn_shapes[i:i + 3]) for i in range(0, len(args.knn_shapes), 3)]
+
+    import math
+
+    import rbl
+
+    doc = {"reps": args.reps, "rounds": args.rounds, "knn": []}
+    for n, d, k in shapes:
+        with rbl.Context(0) as ctx:
+            ctx.set_matrix_kernel(points(n, d), "rbf", args.gamma)
+            runs = {"knn": lambda: ctx.bench_kernel_knn(k, reps=args.reps),
+                    "symmetric_b32": lambda: ctx.bench_kernel_pass(32, args.reps)}
+            for fn in runs.values():
+                fn()                                              # warm both once
+            times = {name: [] for name in runs}
+            for _ in range(args.rounds):
+                for name, fn in runs.items():
+                    times[name].append(fn())
+        row = {"n": n, "d": d, "k": k, "splits": rbl.cross_splits(n, n, d)}
+        for name, t in times.items():
+            row[f"ms_{name}"] = statistics.median(t)
+            row[f"ms_{name}_rounds"] = t
+        row["pairs_per_s"] = n * n / (row["ms_knn"] * 1e-3)
+        row["knn_over_symmetric_b32"] = row["ms_knn"] / row["ms_symmetric_b32"]
+        row["insertions_per_row_estimate"] = k * (1.0 + math.log(n / k))
+        doc["knn"].append(row)
+        print(json.dumps(row), flush=True)
+    out = args.out if args.out else os.path.join(ROOT, "profiles", "kernelop_knn_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--knn", action="store_true",
+                    help="time the neighbour search instead (profiles/kernelop_knn_bench.json)")
+    ap.add_argument("--knn-shapes", type=int, nargs="+", default=[32768, 16, 16, 131072, 16, 16],
+                    help="n d k triples of --knn")
     ap.add_argument("--hadamard", action="store_true",
                     help="time the derivative product instead (profiles/kernelop_hadamard_bench.json)")
     ap.add_argument("--hadamard-shapes", type=int, nargs="+",
@@ -180,6 +229,8 @@ def main():
     ap.add_argument("--out", default=None,
                     help="default profiles/kernelop_bench.json, profiles/kernelop_cross_bench.json with --cross")
     args = ap.parse_args()
+    if args.knn:
+        return knn(args)
     if args.cross:
         return cross(args)
     if args.hadamard:
