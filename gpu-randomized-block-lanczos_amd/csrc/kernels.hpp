@@ -499,6 +499,47 @@ bool kernop_knn(const KernKnn& op, int32_t* idx, double* d2, int32_t* part_idx, 
 bool kernop_knn_counts(unsigned long long out[2], bool reset);
 #endif
 
+// --- kmeans.hip: Lloyd's k-means and k-means++ seeding (rbl_kmeans_run, rbl_kmeans_seed) ----------
+// The points as KernOp holds them (row-major n x d4, zero-padded columns, norms from kernop_norms),
+// n < 2^31 - 64; the centres c x d4 alike, 1 <= c <= kKmeansMaxClusters.
+constexpr int kKmeansMaxClusters = 256;
+struct KmeansPoints {
+  int64_t n = 0;
+  int d4 = 0;
+  const double* X = nullptr;
+  const double* nrm = nullptr;
+};
+// The summation geometry of the update, a function of (n, d4, c) alone: `slabs` row slabs of rows_per
+// rows, each walked by `rl` row lanes (contiguous sub-slabs, ascending rows), the centres in `tiles`
+// tiles of cw (a row is read by the tile of its label only); the record of a slab and of the whole is
+// len = c d4 + c + 2 doubles: the sums row-major, the counts, the inertia, the changed labels.
+struct KmeansGeometry {
+  int slabs = 1, rl = 1, cw = 1, tiles = 1, lds_bytes = 0;
+  int64_t rows_per = 0, len = 0;
+};
+KmeansGeometry kmeans_geometry(int64_t n, int d4, int c);
+// label_i = the j with the smallest (d2(i, j), j), d2 = max((|x_i|^2 + |c_j|^2) - 2 x_i.c_j, 0) from
+// the MFMA chain of kernop_knn; dmin_i = d2(i, label_i).  label may be null.  No atomics; the answer
+// does not depend on the grid.  false: bad shape (nothing launched).
+bool kmeans_assign(const KmeansPoints& P, int c, const double* C, const double* cnrm, int32_t* label, double* dmin,
+                   hipStream_t s);
+// tot (len doubles) <- the record of the labels: part holds slabs x len doubles.  `changed` counts
+// label_i != prev_i.  Fixed order, no atomics.
+bool kmeans_update(const KmeansPoints& P, int c, const int32_t* label, const int32_t* prev, const double* dmin,
+                   double* part, double* tot, hipStream_t s);
+// Cnew_j = sum_j / count_j (Cold_j where count_j = 0) with its norms; rec = {inertia, changed,
+// |Cnew - Cold|_F^2} (3 doubles)
+void kmeans_form(int c, int d4, const double* tot, const double* Cold, double* Cnew, double* cnrm_new, double* rec,
+                 hipStream_t s);
+void kmeans_fill_labels(int64_t n, int32_t v, int32_t* label, hipStream_t s);
+// Seeding round r >= 1 after the pick `last` of round r - 1: w_i <- min(w_i, d2(i, last)) (r = 1: the
+// distance itself), 0 at `last`; picked[r] <- the smallest i whose inclusive prefix sum of w exceeds
+// u total (total = 0: the smallest index not in picked[0 .. r)).  dnew and w: n doubles; slabtot:
+// kmeans_seed_slabs(n) doubles.
+int64_t kmeans_seed_slabs(int64_t n);
+bool kmeans_seed_round(const KmeansPoints& P, int r, int64_t last, double u, double* dnew, double* w,
+                       double* slabtot, int32_t* picked, hipStream_t s);
+
 // --- kernelop_hadamard.hip: kernel-matrix derivative products (rbl_kernel_hadamard) ---------------
 // U = (Phi o A B^T) Q over the points of op (its scale and nugget do not enter): Phi_ij = kappa or one
 // of its derivatives (the values of RBL_KWEIGHT_*; kernelop_dev.hpp phi), Ap and Bp the n x r factors

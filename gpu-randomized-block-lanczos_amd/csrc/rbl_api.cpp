@@ -259,6 +259,10 @@ struct CtxBufs {
   DevBuf<int> d_upd32;       // [skip fp32 kernel, skip fp64 kernel, taken, refused, shadow panels
                              //  read, panels rounded into the shadow]
   DevBuf<double> d_upd32_g;  // the gate's value g of step i at [i % kUpd32Log] (diagnostics)
+  // k-means points (rbl_kmeans_set_points; kmeans.hip): row-major km_n x km_d4 (zero-padded columns)
+  // and their squared norms.  Independent of the matrix: set_matrix and free_matrix leave them alone.
+  DevBuf<double> d_km_x;
+  DevBuf<double> d_km_nrm;
 };
 
 }  // namespace rbl::api
@@ -322,6 +326,9 @@ struct rbl_ctx : rbl::api::MatrixBufs, rbl::api::RunBufs, rbl::api::CtxBufs {
   bool kernop = false;
   int kern_d = 0, kern_d4 = 0, kern_kind = 0, kern_degree = 0;
   double kern_gamma = 0.0, kern_coef0 = 0.0, kern_nugget = 0.0;
+  // k-means points (rbl_kmeans_set_points): km_n points in km_d dimensions; km_n = 0: none
+  int64_t km_n = 0;
+  int km_d = 0, km_d4 = 0;
   // implicit symmetric low-rank update (rbl_set_lowrank): the operator is A + P S P^T, applied
   // by apply_A after the SpMM
   int lr_r = 0, lr_rp = 0;
@@ -3797,6 +3804,213 @@ int rbl_bench_kernel_knn(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, 
             cnt[0] / reps, cnt[1] / reps);
 #endif
   if (st != RBL_OK) return fail(ctx, st, "rbl_bench_kernel_knn: a HIP call failed");
+  return RBL_OK;
+}
+
+// ---- k-means (kmeans.hip): the points live in the context, beside whatever matrix it holds ---------
+namespace {
+static_assert(RBL_KMEANS_MAX_CLUSTERS == kKmeansMaxClusters, "rbl_hip.h and kernels.hpp name the same largest c");
+
+// The buffers of one Lloyd run (rbl_kmeans_run, rbl_bench_kmeans_iter): they live as long as the call —
+// the two centre arrays (C_t and C_{t+1}) with their norms, the two label arrays (labels_t and
+// labels_{t-1}), d2(i, label_i), the slabs' records, the reduced record and the decision record.
+struct KmeansBufs {
+  DevBuf<double> cen[2], cnrm[2], dmin, part, tot, rec;
+  DevBuf<int32_t> lab[2];
+};
+
+void km_points(const rbl_ctx* ctx, KmeansPoints& P) {
+  P.n = ctx->km_n, P.d4 = ctx->km_d4, P.X = ctx->d_km_x, P.nrm = ctx->d_km_nrm;
+}
+
+// what rbl_kmeans_run and the bench hook check, in one order; on RBL_OK cr holds C0 row-major c x d4
+int km_check(rbl_ctx* ctx, const char* who, int c, const double* C0, int64_t ldc0, std::vector<double>& cr) {
+  const std::string w(who);
+  if (ctx->km_n == 0) return fail(ctx, RBL_ERR_STATE, w + ": no points set (rbl_kmeans_set_points)");
+  if (c < 1 || c > RBL_KMEANS_MAX_CLUSTERS || c > ctx->km_n)
+    return fail(ctx, RBL_ERR_INVALID, w + ": c must be in [1," + std::to_string(RBL_KMEANS_MAX_CLUSTERS) +
+                                          "] and at most n");
+  if (!C0 || ldc0 < c) return fail(ctx, RBL_ERR_INVALID, w + ": NULL centres or ldc0 < c");
+  if (!cross_points(c, ctx->km_d, ctx->km_d4, C0, ldc0, cr))
+    return fail(ctx, RBL_ERR_INVALID, w + ": a centre has a non-finite entry");
+  return RBL_OK;
+}
+
+int km_setup(rbl_ctx* ctx, int c, const std::vector<double>& cr, KmeansBufs& B, KmeansGeometry& g) {
+  const int64_t n = ctx->km_n;
+  const int d4 = ctx->km_d4;
+  g = kmeans_geometry(n, d4, c);
+  for (int k = 0; k < 2; ++k) {
+    HIPC(B.cen[k].alloc((size_t)c * d4));
+    HIPC(B.cnrm[k].alloc((size_t)c));
+    HIPC(B.lab[k].alloc((size_t)n));
+  }
+  HIPC(B.dmin.alloc((size_t)n));
+  HIPC(B.part.alloc((size_t)g.slabs * g.len));
+  HIPC(B.tot.alloc((size_t)g.len));
+  HIPC(B.rec.alloc(3));
+  HIPC(hipMemcpyAsync(B.cen[0], cr.data(), cr.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  kernop_norms(c, d4, B.cen[0], B.cnrm[0], ctx->stream);
+  kmeans_fill_labels(n, -1, B.lab[1], ctx->stream);   // "labels_{-1}": every label of t = 0 counts as changed
+  return RBL_OK;
+}
+
+// iteration t against the centres in slot cur: labels into lab[t & 1], the record, C_{t+1} into the other slot
+bool km_iteration(rbl_ctx* ctx, int c, KmeansBufs& B, int t, int cur) {
+  KmeansPoints P;
+  km_points(ctx, P);
+  if (!kmeans_assign(P, c, B.cen[cur], B.cnrm[cur], B.lab[t & 1], B.dmin, ctx->stream)) return false;
+  if (!kmeans_update(P, c, B.lab[t & 1], B.lab[(t + 1) & 1], B.dmin, B.part, B.tot, ctx->stream)) return false;
+  kmeans_form(c, P.d4, B.tot, B.cen[cur], B.cen[cur ^ 1], B.cnrm[cur ^ 1], B.rec, ctx->stream);
+  return true;
+}
+}  // namespace
+
+int rbl_kmeans_set_points(rbl_ctx* ctx, int64_t n, int d, const double* X, int64_t ldx) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (n < 1 || n > (int64_t)INT32_MAX - 64 || d < 1 || d > RBL_KERNOP_MAX_DIM)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_set_points: n must be in [1, 2^31 - 65] and d in [1," +
+                                          std::to_string(RBL_KERNOP_MAX_DIM) + "]");
+  if (!X || ldx < n) return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_set_points: NULL points or ldx < n");
+  const int d4 = 4 * ((d + 3) / 4);
+  std::vector<double> xr;
+  if (!cross_points(n, d, d4, X, ldx, xr))
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_set_points: X has a non-finite entry");
+  HIPC(hipSetDevice(ctx->device));
+  DevBuf<double> x, nrm;   // the context changes only once everything has succeeded
+  HIPC(x.alloc((size_t)n * d4));
+  HIPC(nrm.alloc((size_t)n));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  HIPC(hipMemcpy(x, xr.data(), xr.size() * sizeof(double), hipMemcpyHostToDevice));
+  kernop_norms(n, d4, x, nrm, ctx->stream);
+  HIPC(hipStreamSynchronize(ctx->stream));
+  ctx->d_km_x = std::move(x);
+  ctx->d_km_nrm = std::move(nrm);
+  ctx->km_n = n, ctx->km_d = d, ctx->km_d4 = d4;
+  return RBL_OK;
+}
+
+int rbl_kmeans_clear(rbl_ctx* ctx) {
+  if (!ctx) return RBL_ERR_INVALID;
+  HIPC(hipSetDevice(ctx->device));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  ctx->d_km_x.reset();
+  ctx->d_km_nrm.reset();
+  ctx->km_n = 0, ctx->km_d = ctx->km_d4 = 0;
+  return RBL_OK;
+}
+
+int rbl_kmeans_seed(rbl_ctx* ctx, int c, const double* uniforms, int32_t* picked_out) {
+  if (!ctx) return RBL_ERR_INVALID;
+  if (ctx->km_n == 0) return fail(ctx, RBL_ERR_STATE, "rbl_kmeans_seed: no points set (rbl_kmeans_set_points)");
+  const int64_t n = ctx->km_n;
+  if (c < 1 || c > RBL_KMEANS_MAX_CLUSTERS || c > n)
+    return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_seed: c must be in [1," + std::to_string(RBL_KMEANS_MAX_CLUSTERS) +
+                                          "] and at most n");
+  if (!uniforms || !picked_out) return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_seed: NULL uniforms or output");
+  for (int r = 0; r < c; ++r)
+    if (!std::isfinite(uniforms[r]) || uniforms[r] < 0.0 || uniforms[r] >= 1.0)
+      return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_seed: every uniform must be finite and in [0, 1)");
+  HIPC(hipSetDevice(ctx->device));
+  DevBuf<double> dnew, w, slabtot;
+  DevBuf<int32_t> picked;
+  HIPC(dnew.alloc((size_t)n));
+  HIPC(w.alloc((size_t)n));
+  HIPC(slabtot.alloc((size_t)kmeans_seed_slabs(n)));
+  HIPC(picked.alloc((size_t)c));
+  std::vector<int32_t> ph((size_t)c);
+  ph[0] = (int32_t)std::min<int64_t>((int64_t)std::floor(uniforms[0] * (double)n), n - 1);
+  HIPC(hipMemcpyAsync(picked, ph.data(), sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  KmeansPoints P;
+  km_points(ctx, P);
+  for (int r = 1; r < c; ++r) {   // the host reads one index per round: the next round's centre
+    if (!kmeans_seed_round(P, r, ph[r - 1], uniforms[r], dnew, w, slabtot, picked, ctx->stream))
+      return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_seed: shape out of range");
+    HIPC(hipMemcpyAsync(&ph[r], picked + r, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    if (ph[r] < 0 || ph[r] >= n) return fail(ctx, RBL_ERR_HIP, "rbl_kmeans_seed: a pick out of range");
+  }
+  HIPC(hipStreamSynchronize(ctx->stream));
+  HIPC(hipGetLastError());
+  std::copy(ph.begin(), ph.end(), picked_out);
+  return RBL_OK;
+}
+
+int rbl_kmeans_run(rbl_ctx* ctx, int c, const double* C0, int64_t ldc0, int max_iter, double tol,
+                   int32_t* labels_out, double* centers_out, int64_t ldc, int64_t* counts_out, double* inertia_out,
+                   int* n_iter_out, int* converged_out) {
+  if (!ctx) return RBL_ERR_INVALID;
+  std::vector<double> cr;
+  CHK(km_check(ctx, "rbl_kmeans_run", c, C0, ldc0, cr));
+  if (max_iter < 0) return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_run: max_iter must be >= 0");
+  if (!std::isfinite(tol) || tol < 0.0) return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_run: tol must be finite and >= 0");
+  if (centers_out && ldc < c) return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_run: ldc < c");
+  HIPC(hipSetDevice(ctx->device));
+  const int64_t n = ctx->km_n;
+  const int d = ctx->km_d, d4 = ctx->km_d4;
+  KmeansBufs B;
+  KmeansGeometry g;
+  CHK(km_setup(ctx, c, cr, B, g));
+  int t = 0, cur = 0, conv = 0;
+  double rec[3] = {0.0, 0.0, 0.0}, shift_prev = 0.0;
+  for (;; ++t, cur ^= 1) {
+    if (!km_iteration(ctx, c, B, t, cur)) return fail(ctx, RBL_ERR_INVALID, "rbl_kmeans_run: shape out of range");
+    // the decision record of iteration t: the one thing the host reads inside the loop
+    HIPC(hipMemcpyAsync(rec, B.rec, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    HIPC(hipGetLastError());
+    if (t >= 1 && rec[1] == 0.0) {
+      conv = 1;
+      break;
+    }
+    if (t >= 1 && tol > 0.0 && shift_prev <= tol) {   // |C_t - C_{t-1}|_F^2, formed with C_t
+      conv = 2;
+      break;
+    }
+    if (t == max_iter) break;
+    shift_prev = rec[2];
+  }
+  // the consistent triple (labels_t, C_t, inertia_t) with counts_t
+  std::vector<double> ch((size_t)c * d4), cnt((size_t)c);
+  HIPC(hipMemcpyAsync(ch.data(), B.cen[cur], ch.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(cnt.data(), B.tot + (size_t)c * d4, (size_t)c * sizeof(double), hipMemcpyDeviceToHost,
+                      ctx->stream));
+  if (labels_out)
+    HIPC(hipMemcpyAsync(labels_out, B.lab[t & 1], (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (int k = 0; centers_out && k < d; ++k)
+    for (int j = 0; j < c; ++j) centers_out[j + k * ldc] = ch[(size_t)j * d4 + k];
+  for (int j = 0; counts_out && j < c; ++j) counts_out[j] = (int64_t)cnt[j];
+  if (inertia_out) *inertia_out = rec[0];
+  if (n_iter_out) *n_iter_out = t;
+  if (converged_out) *converged_out = conv;
+  return RBL_OK;
+}
+
+int rbl_bench_kmeans_iter(rbl_ctx* ctx, int c, const double* C0, int64_t ldc0, int reps, double* ms) {
+  if (!ctx) return RBL_ERR_INVALID;
+  std::vector<double> cr;
+  CHK(km_check(ctx, "rbl_bench_kmeans_iter", c, C0, ldc0, cr));
+  if (reps < 1 || !ms) return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kmeans_iter: reps must be >= 1 and ms not NULL");
+  HIPC(hipSetDevice(ctx->device));
+  KmeansBufs B;
+  KmeansGeometry g;
+  CHK(km_setup(ctx, c, cr, B, g));
+  if (!km_iteration(ctx, c, B, 0, 0))  // warm-up
+    return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kmeans_iter: shape out of range");
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  HIPC(hipEventCreate(&e1));
+  int st = RBL_OK;
+  if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+  for (int r = 0; r < reps; ++r) km_iteration(ctx, c, B, r + 1, 0);   // every iteration against C0
+  if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+  float t = 0.f;
+  if (hipEventElapsedTime(&t, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+  *ms = (double)t / reps;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_kmeans_iter: a HIP call failed");
   return RBL_OK;
 }
 

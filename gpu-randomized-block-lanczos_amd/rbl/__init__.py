@@ -20,7 +20,9 @@ cross-kernel product ``Context.kernel_cross``; ``kernel_gradients`` and ``GPMode
 hyperparameter gradients through the derivative product ``Context.kernel_hadamard``; ``knn_graph(X, m)``
 (``rbl.knn``: ``knn_lists``, ``graph_from_knn``) builds the m-nearest-neighbour graph of the points on the
 device (``Context.kernel_knn``) as a sparse A, and ``RBL_spectral_embedding`` / ``spectral_embedding_fit`` take
-``neighbors=m`` to run on it; ``solve(A, B, shift=)`` (``rbl.solve``) solves
+``neighbors=m`` to run on it; ``kmeans(X, c)`` (``rbl.kmeans``) is Lloyd's iteration with k-means++
+seeding on the device, and ``RBL_spectral_clustering`` / ``spectral_clustering_fit`` run it on the
+embedding and return labels; ``solve(A, B, shift=)`` (``rbl.solve``) solves
 (A + shift I) X = B on any of these operators by batched preconditioned CG
 (``spectral_preconditioner``, ``cg_tridiag``, ``logdet_lanczos``); ``Context`` wraps the C-ABI of
 librbl_hip.so (include/rbl_hip.h).  Importing this package loads the HIP library and fails
@@ -48,6 +50,8 @@ from .kernelop import (GPModel, KernelGradient, KernelMatrix, KernelPCAModel, ML
                        row_normalize, scale_gradient_sums, spectral_embedding_fit)
 from .knn import (KnnSpectralEmbeddingModel, graph_from_knn, knn_graph, knn_lists,  # noqa: F401
                   knn_nystrom_algebra, knn_weights, normalized_affinity)
+from .kmeans import (KMeansResult, RBL_spectral_clustering, SpectralClusteringModel, kmeans,  # noqa: F401
+                     kmeans_predict, seeding_uniforms, select_best, spectral_clustering_fit)
 from .funm import (DiagResult, apply_function, cheb_coeffs, cheb_fit, diag_function, diag_series,  # noqa: F401
                    heat_kernel_signature, local_density, logdet, subgraph_centrality, trace_function)
 from .solve import (SolveInfo, cg_tridiag, lanczos_quadrature, logdet_lanczos, solve,  # noqa: F401

@@ -74,6 +74,8 @@ RBL_KWEIGHT_DGAMMA = 1
 RBL_KWEIGHT_DSCALE = 2
 # rbl_kernel_knn: the largest k
 RBL_KNN_MAX = 64
+# rbl_kmeans_run / rbl_kmeans_seed: the largest number of clusters
+RBL_KMEANS_MAX_CLUSTERS = 256
 # rbl_cheb_diag: the block drawn when X is NULL
 RBL_PROBE_GAUSS = 0
 RBL_PROBE_SIGN = 1
@@ -133,6 +135,12 @@ SIGNATURES = {
     "rbl_bench_kernel_knn": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, C.c_int, _pd]),
     "rbl_kernel_hadamard": (C.c_int, [_p, C.c_int, C.c_int, _pd, _i64, _pd, _i64, C.c_int, _pd, _i64, _pd, _i64]),
     "rbl_bench_kernel_hadamard": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _pd]),
+    "rbl_kmeans_set_points": (C.c_int, [_p, _i64, C.c_int, _pd, _i64]),
+    "rbl_kmeans_clear": (C.c_int, [_p]),
+    "rbl_kmeans_seed": (C.c_int, [_p, C.c_int, _pd, _pi32]),
+    "rbl_kmeans_run": (C.c_int, [_p, C.c_int, _pd, _i64, C.c_int, C.c_double, _pi32, _pd, _i64, _pi64, _pd,
+                                 C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rbl_bench_kmeans_iter": (C.c_int, [_p, C.c_int, _pd, _i64, C.c_int, _pd]),
     "rbl_gen_matrix_hashwindow": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_circuit": (C.c_int, [_p, _i64, _i64, C.c_double, _u64, C.c_int, _pd]),
     "rbl_gen_matrix_rmat": (C.c_int, [_p, _i64, C.c_int, _i64, C.c_double, C.c_double, C.c_double,

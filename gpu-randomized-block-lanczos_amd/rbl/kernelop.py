@@ -202,7 +202,8 @@ def RBL_spectral_embedding(X, k: int, b: int, *, kind: str = "rbf", gamma: float
     eigenpairs of D^-1/2 K D^-1/2 with D = diag(K 1).  The degrees come from one product with the
     ones vector and enter as the operator's scale, so K is never formed.  Returns (lam, V, Y): lam
     descending, V n x k, Y the rows of V normalised to unit length — points of one cluster share a
-    direction, so any clustering of Y's rows (k-means is not part of this library) labels them.
+    direction, so any clustering of Y's rows labels them (``rbl.RBL_spectral_clustering`` runs the
+    device k-means of ``rbl.kmeans`` on them and returns the labels).
 
     neighbors=m: the affinity is the m-nearest-neighbour graph of the points instead (``rbl.knn``:
     one device sweep builds the lists, ``graph_from_knn`` with ``mode`` and ``weight`` the graph A;

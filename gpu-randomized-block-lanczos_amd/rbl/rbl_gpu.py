@@ -404,6 +404,89 @@ class Context:
                     "rbl_bench_kernel_hadamard")
         return float(ms[0])
 
+    # -- k-means on the device: the points are the context's own, beside whatever matrix it holds --
+    def kmeans_set_points(self, X) -> None:
+        """The n x d points of the k-means entries (rbl_kmeans_set_points): copied to the device once;
+        the matrix, the basis and the options of the context are left as they were."""
+        from .kmeans import _points
+        X = np.asfortranarray(_points("kmeans_set_points", X))
+        n, d = X.shape
+        self._check(lib.rbl_kmeans_set_points(self._h, n, d, dptr(X), n), "rbl_kmeans_set_points")
+        self._km_shape = (n, d)
+
+    def kmeans_clear(self) -> None:
+        """Release the k-means points (rbl_kmeans_clear)."""
+        self._check(lib.rbl_kmeans_clear(self._h), "rbl_kmeans_clear")
+        self._km_shape = None
+
+    def _kmeans_shape(self, what):
+        shape = getattr(self, "_km_shape", None)
+        if shape is None:
+            raise ValueError(f"{what}: no points set (kmeans_set_points)")
+        return shape
+
+    def kmeans_seed(self, n_clusters: int, uniforms) -> np.ndarray:
+        """Plain k-means++ over the points set (rbl_kmeans_seed) from n_clusters uniforms in [0, 1):
+        the int32 indices of the picked points.  Round 0 picks min(floor(u_0 n), n - 1); round r the
+        smallest i whose inclusive prefix sum of w_i = min over the picked points of d2(i, .) exceeds
+        u_r total.  Two calls give the same bits."""
+        from .kmeans import _check_clusters
+        n, _ = self._kmeans_shape("kmeans_seed")
+        c = _check_clusters("kmeans_seed", n_clusters, n)
+        u = np.ascontiguousarray(uniforms, dtype=np.float64).ravel()
+        if u.size != c:
+            raise ValueError(f"kmeans_seed: needs n_clusters = {c} uniforms, got {u.size}")
+        if not np.all(np.isfinite(u)) or np.any(u < 0.0) or np.any(u >= 1.0):
+            raise ValueError("kmeans_seed: every uniform must be finite and in [0, 1)")
+        picked = np.zeros(c, dtype=np.int32)
+        self._check(lib.rbl_kmeans_seed(self._h, c, dptr(u), i32ptr(picked)), "rbl_kmeans_seed")
+        return picked
+
+    def _kmeans_centres(self, what, C0):
+        from .kmeans import _check_clusters
+        n, d = self._kmeans_shape(what)
+        C0 = np.asarray(C0, dtype=np.float64)
+        if C0.ndim == 1 and d == 1:
+            C0 = C0.reshape(-1, 1)
+        if C0.ndim != 2 or C0.shape[1] != d:
+            raise ValueError(f"{what}: the centres must be a c x d array with d = {d}")
+        c = _check_clusters(what, C0.shape[0], n)
+        if not np.all(np.isfinite(C0)):
+            raise ValueError(f"{what}: a centre has a non-finite entry")
+        return np.asfortranarray(C0), c, n, d
+
+    def kmeans_run(self, C0, max_iter: int = 300, tol: float = 0.0):
+        """Lloyd's iteration over the points set from the centres C0 (c x d) (rbl_kmeans_run): a
+        ``rbl.kmeans.KMeansResult`` with the consistent triple (labels_t, C_t, inertia_t), counts_t,
+        n_iter = t and converged (1: no label changed, 2: |C_t - C_{t-1}|_F^2 <= tol, 0: max_iter
+        reached).  max_iter = 0 assigns only.  A point goes to the centre with the smallest
+        (d2, index); a centre without points keeps its value.  Two calls give the same bits."""
+        import ctypes as C
+        from .kmeans import KMeansResult
+        C0, c, n, d = self._kmeans_centres("kmeans_run", C0)
+        if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 0:
+            raise ValueError("kmeans_run: max_iter must be an integer >= 0")
+        if not np.isfinite(tol) or tol < 0.0:
+            raise ValueError("kmeans_run: tol must be finite and >= 0")
+        labels = np.zeros(n, dtype=np.int32)
+        centers = np.zeros((c, d), order="F")
+        counts = np.zeros(c, dtype=np.int64)
+        inertia = np.zeros(1)
+        n_iter, conv = C.c_int(0), C.c_int(0)
+        self._check(lib.rbl_kmeans_run(self._h, c, dptr(C0), c, int(max_iter), float(tol), i32ptr(labels),
+                                       dptr(centers), c, i64ptr(counts), dptr(inertia), C.byref(n_iter),
+                                       C.byref(conv)), "rbl_kmeans_run")
+        return KMeansResult(labels, np.ascontiguousarray(centers), float(inertia[0]), counts, n_iter.value,
+                            conv.value)
+
+    def bench_kmeans_iter(self, C0, reps: int = 5) -> float:
+        """Milliseconds per Lloyd iteration over the points set against the centres C0
+        (rbl_bench_kmeans_iter)."""
+        C0, c, _, _ = self._kmeans_centres("bench_kmeans_iter", C0)
+        ms = np.zeros(1)
+        self._check(lib.rbl_bench_kmeans_iter(self._h, c, dptr(C0), c, int(reps), dptr(ms)), "rbl_bench_kmeans_iter")
+        return float(ms[0])
+
     # -- implicit symmetric low-rank update: the operator A + P S P^T ------------------------
     def set_lowrank(self, P, S) -> None:
         """The operator becomes A + P S P^T (rbl_set_lowrank): P n x r, S r x r symmetric,

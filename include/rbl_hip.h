@@ -459,6 +459,52 @@ int rbl_kernel_hadamard(rbl_ctx* ctx, int mode, int r, const double* A, int64_t 
  * columns and a block of b columns (the device part of rbl_kernel_hadamard alone): one warm-up, then
  * `reps` products between two hipEvents. */
 int rbl_bench_kernel_hadamard(rbl_ctx* ctx, int mode, int r, int b, int reps, double* ms);
+/* k-means on the device (csrc/kmeans.hip): Lloyd's iteration and k-means++ seeding over n points in d
+ * dimensions, fp64, one GPU.  The points are the context's own, beside whatever matrix it holds:
+ * setting or clearing them leaves the matrix, the basis and every option as they were.
+ *
+ * rbl_kmeans_set_points: X n x d column-major with leading dimension ldx >= n (host), 1 <= n < 2^31 - 64,
+ * 1 <= d <= RBL_KERNOP_MAX_DIM, every entry finite; copied to the device (row-major, the columns
+ * zero-padded to a multiple of 4, with their squared norms).  Replaces points set before.
+ * rbl_kmeans_clear: releases them (no error when none are set).
+ *
+ * Distances are taken in the Gram form of rbl_kernel_knn,
+ *     d2(i, j) = max((|x_i|^2 + |c_j|^2) - 2 x_i.c_j, 0),
+ * the inner product a fixed-order fp64 MFMA chain, and a point goes to the centre with the smallest
+ * (d2, j): the smaller index wins a tie.  Centre X first where its mean is far from 0.  Sums, counts,
+ * inertia and the number of changed labels are added in an order that depends on (n, d, c) alone,
+ * without atomics: two calls give the same bits, on any device.
+ *
+ * rbl_kmeans_run: C0 c x d column-major (ldc0 >= c), 1 <= c <= RBL_KMEANS_MAX_CLUSTERS, c <= n.  At
+ * iteration t = 0, 1, ...: assign to C_t (labels_t, counts_t, inertia_t = sum_i d2(i, label_i),
+ * changed_t = #{i: label_i differs from iteration t - 1}); stop with *converged_out = 1 if t >= 1 and
+ * changed_t = 0; with 2 if t >= 1, tol > 0 and |C_t - C_{t-1}|_F^2 <= tol; with 0 if t = max_iter;
+ * otherwise C_{t+1}: centre_j = (sum of its points) / count_j by an IEEE division, a centre with
+ * count_j = 0 keeping its value.  Returned: the consistent triple labels_t (n int32), C_t (c x d
+ * column-major, ldc >= c) and inertia_t, with counts_t (c int64) and *n_iter_out = t.  max_iter = 0
+ * assigns only.  Any output may be NULL.  The host reads three doubles per iteration; nothing of size n
+ * crosses PCIe inside the loop.
+ *
+ * rbl_kmeans_seed: plain k-means++ from the c uniforms u_r in [0, 1): round 0 picks
+ * min(floor(u_0 n), n - 1); round r keeps w_i = min over the picked points of d2(i, .), 0 by index for a
+ * picked point, and picks the smallest i whose inclusive prefix sum of w (a fixed order, a function of
+ * n alone) exceeds u_r total — the smallest index not yet picked when total = 0.  picked_out: c int32
+ * indices into the points.
+ *
+ * RBL_ERR_STATE when no points are set; RBL_ERR_INVALID for d or c out of range, c > n, a NULL input,
+ * a leading dimension below its rows, a non-finite point, centre, uniform or tol, a uniform outside
+ * [0, 1), tol < 0 or max_iter < 0 — the context and the stored points unchanged. */
+#define RBL_KMEANS_MAX_CLUSTERS 256
+int rbl_kmeans_set_points(rbl_ctx* ctx, int64_t n, int d, const double* X, int64_t ldx);
+int rbl_kmeans_clear(rbl_ctx* ctx);
+int rbl_kmeans_seed(rbl_ctx* ctx, int c, const double* uniforms, int32_t* picked_out);
+int rbl_kmeans_run(rbl_ctx* ctx, int c, const double* C0, int64_t ldc0, int max_iter, double tol,
+                   int32_t* labels_out, double* centers_out, int64_t ldc, int64_t* counts_out,
+                   double* inertia_out, int* n_iter_out, int* converged_out);
+/* Milliseconds per Lloyd iteration (assignment, update, reduction and the new centres; the device part
+ * of rbl_kmeans_run alone) over the points set, every iteration against the centres C0: one warm-up,
+ * then `reps` iterations between two hipEvents. */
+int rbl_bench_kmeans_iter(rbl_ctx* ctx, int c, const double* C0, int64_t ldc0, int reps, double* ms);
 int rbl_gen_matrix_hashwindow(rbl_ctx* ctx, int64_t n, int64_t halfwidth, double density,
                               uint64_t seed, int nplant, const double* plant);
 /* Device-side generator of the seeded symmetric R-MAT matrix (BASELINE

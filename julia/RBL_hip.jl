@@ -392,6 +392,56 @@ function RBL_gpu_knn(X::Matrix{Float64}, k::Int; Z = nothing, device::Int = 0)
     end
 end
 
+# k-means of the rows of X (n x d) into c clusters on the device (rbl_kmeans_*): Lloyd's iteration from
+# the centres `init` (c x d), or with init = nothing from plain k-means++ seeding on the device with the c
+# uniforms rand(Random.MersenneTwister(seed), c).  A point goes to the centre with the smallest (squared
+# distance, index); a centre that loses all its points keeps its value (counts shows it).  The loop stops
+# when no label changes (converged = 1), when the centres moved by at most tol in squared Frobenius norm
+# (2; tol = 0: never), or after max_iter iterations (0); max_iter = 0 assigns only.  Returns labels
+# (1-based), centers (c x d), inertia, counts, n_iter and converged.  The distance is taken in Gram form:
+# centre X first where its mean is far from 0.  One context: rbl_kmeans_set_points, rbl_kmeans_seed,
+# rbl_kmeans_run, rbl_kmeans_clear, free.
+import Random
+
+function RBL_gpu_kmeans(X::Matrix{Float64}, c::Int; init = nothing, max_iter::Int = 300, tol::Float64 = 0.0,
+                        seed::Int = 0, device::Int = 0)
+    n, d = size(X)
+    ctx = rbl_context(device)
+    try
+        rbl_check(ctx, ccall((:rbl_kmeans_set_points, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Int64, Cint, Ptr{Float64}, Int64), ctx, n, Cint(d), X, n),
+                  "rbl_kmeans_set_points")
+        C0 = init
+        if C0 === nothing
+            u = rand(Random.MersenneTwister(seed), c)
+            picked = zeros(Int32, c)
+            rbl_check(ctx, ccall((:rbl_kmeans_seed, librbl_hip), Cint,
+                                 (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Int32}), ctx, Cint(c), u, picked),
+                      "rbl_kmeans_seed")
+            C0 = X[Int.(picked) .+ 1, :]
+        end
+        size(C0) == (c, d) || throw(ArgumentError("RBL_gpu_kmeans: init must be $c x $d"))
+        C0 = Matrix{Float64}(C0)
+        labels = zeros(Int32, n)
+        centers = zeros(Float64, c, d)
+        counts = zeros(Int64, c)
+        inertia = zeros(Float64, 1)
+        n_iter = zeros(Cint, 1)
+        converged = zeros(Cint, 1)
+        rbl_check(ctx, ccall((:rbl_kmeans_run, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Cint, Float64, Ptr{Int32}, Ptr{Float64}, Int64,
+                              Ptr{Int64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}),
+                             ctx, Cint(c), C0, c, Cint(max_iter), tol, labels, centers, c, counts, inertia, n_iter,
+                             converged),
+                  "rbl_kmeans_run")
+        rbl_check(ctx, ccall((:rbl_kmeans_clear, librbl_hip), Cint, (Ptr{Cvoid},), ctx), "rbl_kmeans_clear")
+        return (labels = labels .+ Int32(1), centers = centers, inertia = inertia[1], counts = counts,
+                n_iter = Int(n_iter[1]), converged = Int(converged[1]))
+    finally
+        ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
+    end
+end
+
 # Kernel-matrix derivative product over the points of the kernel matrix a context holds
 # (rbl_kernel_hadamard): U (n x b) = (Phi o A B^T) Q with A, B n x r and Q n x b; weight = :value
 # Phi = kappa, :dgamma d kappa / d gamma, :dscale the factor psi of d kappa / d log s_k (times

@@ -15,7 +15,8 @@ Writes one JSON document (default profiles/kernelop_bench.json).
 
 --cross times the cross-kernel product kappa(Z, X) W (kernelop_cross.hip) instead: see cross();
 --hadamard the derivative product (Phi o A B^T) Q (kernelop_hadamard.hip): see hadamard();
---knn the k-nearest-neighbour search (kernelop_knn.hip): see knn()."""
+--knn the k-nearest-neighbour search (kernelop_knn.hip): see knn();
+--kmeans one Lloyd iteration (kmeans.hip) and the labels' share of spectral clustering: see kmeans()."""
 import argparse
 import json
 import os
@@ -200,8 +201,85 @@ def knn(args):
     print("wrote", out)
 
 
+def blobs(n, d, c, seed=0):
+    """c Gaussian blobs (kmeans_ref.generate's recipe), mean-centred, and c of the points as centres."""
+    rng = np.random.default_rng(seed)
+    mu = 3.0 * rng.standard_normal((c, d))
+    X = mu[np.arange(n) % c] + 0.5 * rng.standard_normal((n, d))
+    X -= X.mean(axis=0)
+    return np.asfortranarray(X), X[np.arange(c) * (n // c)].copy()
+
+
+def kmeans(args):
+    """--kmeans: rbl_bench_kmeans_iter (hipEvents around `--reps` Lloyd iterations after one warm-up)
+    for each (n, d, c) of --kmeans-shapes, beside two yardsticks from the same process: the k = 1
+    cross-mode rbl_bench_kernel_knn of the n points against the c centres (the assignment alone, by the
+    list kernel), and the model n d4 8 bytes per read of the points and 2 n c d4 flops.  The two timings
+    alternate within a round; medians over `--rounds` rounds.  With --kmeans-e2e N the wall time of
+    RBL_spectral_clustering (neighbors=16, n_clusters=8, n_init=10) and of RBL_spectral_embedding alone
+    over N three-blob points in 16 dimensions, after a small warm-up call."""
+    if len(args.kmeans_shapes) % 3:
+        raise SystemExit("--kmeans-shapes takes n d c triples")
+    shapes = [tuple(args.kmeans_shapes[i:i + 3]) for i in range(0, len(args.kmeans_shapes), 3)]
+
+    import rbl
+
+    doc = {"reps": args.reps, "rounds": args.rounds, "kmeans": []}
+    for n, d, c in shapes:
+        X, C0 = blobs(n, d, c)
+        d4 = 4 * ((d + 3) // 4)
+        with rbl.Context(0) as ctx:
+            ctx.kmeans_set_points(X)
+            ctx.set_matrix_kernel(C0, "rbf", args.gamma)          # the centres as the column points of the search
+            runs = {"lloyd_iteration": lambda: ctx.bench_kmeans_iter(C0, reps=args.reps),
+                    "knn_k1_cross": lambda: ctx.bench_kernel_knn(1, X, reps=args.reps)}
+            for fn in runs.values():
+                fn()                                              # warm both once
+            times = {name: [] for name in runs}
+            for _ in range(args.rounds):
+                for name, fn in runs.items():
+                    times[name].append(fn())
+        row = {"n": n, "d": d, "c": c, "knn_splits": rbl.cross_splits(n, c, d)}
+        for name, t in times.items():
+            row[f"ms_{name}"] = statistics.median(t)
+            row[f"ms_{name}_rounds"] = t
+        t = row["ms_lloyd_iteration"] * 1e-3
+        row["bytes_per_read_of_points"] = n * d4 * 8
+        row["flops"] = 2 * n * c * d4
+        row["tb_per_s_two_reads"] = 2 * n * d4 * 8 / t / 1e12
+        row["tflops"] = 2 * n * c * d4 / t / 1e12
+        row["iteration_over_knn"] = row["ms_lloyd_iteration"] / row["ms_knn_k1_cross"]
+        doc["kmeans"].append(row)
+        print(json.dumps(row), flush=True)
+    if args.kmeans_e2e:
+        n = args.kmeans_e2e
+        rng = np.random.default_rng(20)
+        X = 4.0 * np.eye(3, 16)[np.arange(n) % 3] + 0.35 * rng.standard_normal((n, 16)) / 4.0
+        X -= X.mean(axis=0)
+        e2e = {"n": n, "d": 16, "neighbors": 16, "n_clusters": 8, "n_init": 10}
+        rbl.RBL_spectral_clustering(X[:4096], 8, 8, neighbors=16, n_init=1)       # warm the process once
+        for name, fn in (("embedding", lambda: rbl.RBL_spectral_embedding(X, 8, 8, neighbors=16)),
+                         ("clustering", lambda: rbl.RBL_spectral_clustering(X, 8, 8, neighbors=16, n_init=10))):
+            t0 = time.perf_counter()
+            fn()
+            e2e[f"wall_s_{name}"] = time.perf_counter() - t0
+        doc["spectral_clustering"] = e2e
+        print(json.dumps(e2e), flush=True)
+    out = args.out if args.out else os.path.join(ROOT, "profiles", "kernelop_kmeans_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kmeans", action="store_true",
+                    help="time one Lloyd iteration instead (profiles/kernelop_kmeans_bench.json)")
+    ap.add_argument("--kmeans-shapes", type=int, nargs="+", default=[131072, 16, 16, 1048576, 64, 256],
+                    help="n d c triples of --kmeans")
+    ap.add_argument("--kmeans-e2e", type=int, default=0,
+                    help="with --kmeans: also the wall time of RBL_spectral_clustering over this many points")
     ap.add_argument("--knn", action="store_true",
                     help="time the neighbour search instead (profiles/kernelop_knn_bench.json)")
     ap.add_argument("--knn-shapes", type=int, nargs="+", default=[32768, 16, 16, 131072, 16, 16],
@@ -229,6 +307,8 @@ def main():
     ap.add_argument("--out", default=None,
                     help="default profiles/kernelop_bench.json, profiles/kernelop_cross_bench.json with --cross")
     args = ap.parse_args()
+    if args.kmeans:
+        return kmeans(args)
     if args.knn:
         return knn(args)
     if args.cross:
