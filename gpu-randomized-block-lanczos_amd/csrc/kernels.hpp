@@ -499,6 +499,37 @@ bool kernop_knn(const KernKnn& op, int32_t* idx, double* d2, int32_t* part_idx, 
 bool kernop_knn_counts(unsigned long long out[2], bool reset);
 #endif
 
+// --- pchol.hip: partial pivoted Cholesky of the kernel matrix (rbl_kernel_pchol) ------------------
+// L L^T ~ diag(scale) K diag(scale) over the points of op (its nugget does not enter), at most R <=
+// min(n, kPcholMaxRank) greedy steps, n <= 2^31 - 65.  Every buffer on the device:
+//   L       ldl x R doubles, column-major, ldl >= n (zeroed by the run; columns past the rank stay 0)
+//   d       n doubles, the residual diagonal
+//   pmax, ptrace, pidx   2 pchol_slabs(n) entries each: the workgroups' partials, two buffers
+//   piv     R int32 (-1 past the rank), trace R + 1 doubles (0 past the rank: the caller repeats the last)
+//   floor_  1 double, rank 1 int32, flag R + 2 int32 (one stop flag per launch)
+constexpr int kPcholMaxRank = 256;
+constexpr int kPcholSlabRows = 256;
+static_assert(kPcholMaxRank <= kPcholSlabRows, "one thread per earlier column stages L[p, 0..j)");
+struct PcholWork {
+  double* L = nullptr;
+  int64_t ldl = 0;
+  double* d = nullptr;
+  double* pmax = nullptr;
+  double* ptrace = nullptr;
+  int32_t* pidx = nullptr;
+  int32_t* piv = nullptr;
+  double* trace = nullptr;
+  double* floor_ = nullptr;
+  int32_t* rank = nullptr;
+  int32_t* flag = nullptr;
+};
+int pchol_slabs(int64_t n);  // ceil(n / kPcholSlabRows): a function of n alone
+// Enqueues the clears, one init launch and R + 1 step launches on s, nothing read back: stop at step j
+// (rank = j) when j == R, !(d_p > 4 (R + 2) 2^-53 dmax0) or trace_j <= tol trace_0.  Fixed summation
+// orders, no atomics, no grid-wide synchronisation.  Each workgroup reads all pchol_slabs(n) partials per
+// step (one reduction level): meant for n up to ~10^6.  false: bad shape or a NULL buffer (nothing launched).
+bool kernop_pchol(const KernOp& op, int R, double tol, const PcholWork& W, hipStream_t s);
+
 // --- kmeans.hip: Lloyd's k-means and k-means++ seeding (rbl_kmeans_run, rbl_kmeans_seed) ----------
 // The points as KernOp holds them (row-major n x d4, zero-padded columns, norms from kernop_norms),
 // n < 2^31 - 64; the centres c x d4 alike, 1 <= c <= kKmeansMaxClusters.

@@ -3807,6 +3807,108 @@ int rbl_bench_kernel_knn(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, 
   return RBL_OK;
 }
 
+// ---- partial pivoted Cholesky of the kernel matrix (pchol.hip) --------------------------------------
+namespace {
+static_assert(RBL_PCHOL_MAX_RANK == kPcholMaxRank, "rbl_hip.h and kernels.hpp name the same largest rank");
+
+// The buffers of one factorisation (rbl_kernel_pchol, rbl_bench_kernel_pchol): they live as long as
+// the call — L column-major n x R, the residual diagonal, the slabs' partials (two buffers) and the
+// small records (trace R + 1 and the floor; piv R, the rank and the R + 2 stop flags).
+struct PcholBufs {
+  DevBuf<double> L, d, part, rec;
+  DevBuf<int32_t> pidx, irec;
+};
+
+// what both entries check, in one order, before anything is allocated
+int pchol_check(rbl_ctx* ctx, const char* who, int max_rank, double tol) {
+  const std::string w(who);
+  if (!ctx->kernop) return fail(ctx, RBL_ERR_STATE, w + ": no kernel matrix");
+  if (max_rank < 1 || max_rank > RBL_PCHOL_MAX_RANK || max_rank > ctx->n)
+    return fail(ctx, RBL_ERR_INVALID, w + ": max_rank must be in [1, min(n, " + std::to_string(RBL_PCHOL_MAX_RANK) + ")]");
+  if (!std::isfinite(tol) || tol < 0.0 || tol >= 1.0)
+    return fail(ctx, RBL_ERR_INVALID, w + ": tol must be finite and in [0, 1)");
+  if (ctx->n > (int64_t)INT32_MAX - 64) return fail(ctx, RBL_ERR_INVALID, w + ": n too large for int32 indices");
+  return RBL_OK;
+}
+
+int pchol_setup(rbl_ctx* ctx, int R, PcholBufs& B, PcholWork& W) {
+  const int64_t n = ctx->n;
+  const size_t G = (size_t)pchol_slabs(n);
+  HIPC(B.L.alloc((size_t)n * R));
+  HIPC(B.d.alloc((size_t)n));
+  HIPC(B.part.alloc(4 * G));
+  HIPC(B.pidx.alloc(2 * G));
+  HIPC(B.rec.alloc((size_t)R + 2));
+  HIPC(B.irec.alloc((size_t)2 * R + 3));
+  W.L = B.L, W.ldl = n, W.d = B.d;
+  W.pmax = B.part, W.ptrace = B.part + 2 * G, W.pidx = B.pidx;
+  W.trace = B.rec, W.floor_ = B.rec + R + 1;
+  W.piv = B.irec, W.rank = B.irec + R, W.flag = B.irec + R + 1;
+  return RBL_OK;
+}
+}  // namespace
+
+int rbl_kernel_pchol(rbl_ctx* ctx, int max_rank, double tol, double* L, int64_t ldl, int32_t* piv, double* trace,
+                     int* rank_out) {
+  if (!ctx) return RBL_ERR_INVALID;
+  CHK(pchol_check(ctx, "rbl_kernel_pchol", max_rank, tol));
+  const int64_t n = ctx->n;
+  if (L && ldl < n) return fail(ctx, RBL_ERR_INVALID, "rbl_kernel_pchol: ldl must be >= n");
+  HIPC(hipSetDevice(ctx->device));
+  const int R = max_rank;
+  PcholBufs B;
+  PcholWork W;
+  CHK(pchol_setup(ctx, R, B, W));
+  if (!kernop_pchol(kernop(ctx), R, tol, W, ctx->stream))
+    return fail(ctx, RBL_ERR_HIP, "rbl_kernel_pchol: the factorisation could not be enqueued");
+  HIPC(hipGetLastError());
+  std::vector<double> th((size_t)R + 1);
+  std::vector<int32_t> ih((size_t)R + 1);  // piv, then the rank
+  HIPC(hipMemcpyAsync(th.data(), W.trace, th.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(ih.data(), W.piv, ih.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (L) HIPC(hipMemcpy2DAsync(L, (size_t)ldl * sizeof(double), W.L, (size_t)n * sizeof(double),
+                               (size_t)n * sizeof(double), (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  const int rank = ih[R];
+  if (rank < 0 || rank > R) return fail(ctx, RBL_ERR_HIP, "rbl_kernel_pchol: the device reported no rank");
+  if (piv) std::copy_n(ih.data(), R, piv);
+  if (trace)
+    for (int j = 0; j <= R; ++j) trace[j] = th[std::min(j, rank)];
+  if (rank_out) *rank_out = rank;
+  return RBL_OK;
+}
+
+int rbl_bench_kernel_pchol(rbl_ctx* ctx, int max_rank, int reps, double* ms) {
+  if (!ctx) return RBL_ERR_INVALID;
+  CHK(pchol_check(ctx, "rbl_bench_kernel_pchol", max_rank, 0.0));
+  if (reps < 1 || !ms) return fail(ctx, RBL_ERR_INVALID, "rbl_bench_kernel_pchol: reps must be >= 1 and ms not NULL");
+  HIPC(hipSetDevice(ctx->device));
+  PcholBufs B;
+  PcholWork W;
+  CHK(pchol_setup(ctx, max_rank, B, W));
+  const KernOp op = kernop(ctx);
+  if (!kernop_pchol(op, max_rank, 0.0, W, ctx->stream))  // warm-up
+    return fail(ctx, RBL_ERR_HIP, "rbl_bench_kernel_pchol: the factorisation could not be enqueued");
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) {
+    (void)hipEventDestroy(e0);
+    return fail(ctx, RBL_ERR_HIP, "rbl_bench_kernel_pchol: hipEventCreate failed");
+  }
+  int st = RBL_OK;
+  if (hipEventRecord(e0, ctx->stream) != hipSuccess) st = RBL_ERR_HIP;
+  for (int r = 0; r < reps; ++r)
+    if (!kernop_pchol(op, max_rank, 0.0, W, ctx->stream)) st = RBL_ERR_HIP;
+  if (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) st = RBL_ERR_HIP;
+  float t = 0.f;
+  if (hipEventElapsedTime(&t, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) st = RBL_ERR_HIP;
+  *ms = (double)t / reps;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (st != RBL_OK) return fail(ctx, st, "rbl_bench_kernel_pchol: a HIP call failed");
+  return RBL_OK;
+}
+
 // ---- k-means (kmeans.hip): the points live in the context, beside whatever matrix it holds ---------
 namespace {
 static_assert(RBL_KMEANS_MAX_CLUSTERS == kKmeansMaxClusters, "rbl_hip.h and kernels.hpp name the same largest c");

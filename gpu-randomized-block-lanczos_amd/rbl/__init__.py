@@ -24,7 +24,10 @@ device (``Context.kernel_knn``) as a sparse A, and ``RBL_spectral_embedding`` / 
 seeding on the device, and ``RBL_spectral_clustering`` / ``spectral_clustering_fit`` run it on the
 embedding and return labels; ``solve(A, B, shift=)`` (``rbl.solve``) solves
 (A + shift I) X = B on any of these operators by batched preconditioned CG
-(``spectral_preconditioner``, ``cg_tridiag``, ``logdet_lanczos``); ``Context`` wraps the C-ABI of
+(``spectral_preconditioner``, ``cg_tridiag``, ``logdet_lanczos``); ``pivoted_cholesky(K, r)``
+(``rbl.pchol``) is the partial pivoted Cholesky factor of a kernel matrix on the device
+(``Context.kernel_pchol``), and ``pchol_preconditioner`` turns it into a CG preconditioner without an
+eigensolve (``gp_fit(..., precond="pchol")``); ``Context`` wraps the C-ABI of
 librbl_hip.so (include/rbl_hip.h).  Importing this package loads the HIP library and fails
 loudly if it has not been built: there is no CPU fallback.
 """
@@ -56,3 +59,5 @@ from .funm import (DiagResult, apply_function, cheb_coeffs, cheb_fit, diag_funct
                    heat_kernel_signature, local_density, logdet, subgraph_centrality, trace_function)
 from .solve import (SolveInfo, cg_tridiag, lanczos_quadrature, logdet_lanczos, solve,  # noqa: F401
                     spectral_preconditioner)
+from .pchol import (PivotedCholesky, pchol_eigenpairs, pchol_preconditioner, pivoted_cholesky,  # noqa: F401
+                    precond_logdet_terms)

@@ -74,6 +74,8 @@ RBL_KWEIGHT_DGAMMA = 1
 RBL_KWEIGHT_DSCALE = 2
 # rbl_kernel_knn: the largest k
 RBL_KNN_MAX = 64
+# rbl_kernel_pchol: the largest rank
+RBL_PCHOL_MAX_RANK = 256
 # rbl_kmeans_run / rbl_kmeans_seed: the largest number of clusters
 RBL_KMEANS_MAX_CLUSTERS = 256
 # rbl_cheb_diag: the block drawn when X is NULL
@@ -133,6 +135,8 @@ SIGNATURES = {
     "rbl_bench_kernel_cross": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _pd]),
     "rbl_kernel_knn": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, _pi32, _i64, _pd, _i64]),
     "rbl_bench_kernel_knn": (C.c_int, [_p, _i64, _pd, _i64, C.c_int, C.c_int, C.c_int, _pd]),
+    "rbl_kernel_pchol": (C.c_int, [_p, C.c_int, C.c_double, _pd, _i64, _pi32, _pd, C.POINTER(C.c_int)]),
+    "rbl_bench_kernel_pchol": (C.c_int, [_p, C.c_int, C.c_int, _pd]),
     "rbl_kernel_hadamard": (C.c_int, [_p, C.c_int, C.c_int, _pd, _i64, _pd, _i64, C.c_int, _pd, _i64, _pd, _i64]),
     "rbl_bench_kernel_hadamard": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _pd]),
     "rbl_kmeans_set_points": (C.c_int, [_p, _i64, C.c_int, _pd, _i64]),

@@ -469,7 +469,7 @@ class GPModel(_KernelFit):
                     var[c0 + j0:c0 + j0 + Cj.shape[1]] -= (Cj * ctx.apply_filter(Cj)).sum(axis=0)
         return mean, np.maximum(var, 0.0)
 
-    def log_marginal_likelihood(self, nvec: int = 64, seed: int = 0):
+    def log_marginal_likelihood(self, nvec: int = 64, seed: int = 0, use_precond: bool = False):
         """(estimate, stderr) of log p(y | X) = -1/2 y^T alpha - 1/2 log det(K + noise I) - n / 2
         log 2 pi, summed over the t columns of y.  The log det term is a Hutchinson estimate over
         nvec Gaussian probes (``rbl.logdet`` on the bounds of the fit); stderr is its standard error
@@ -477,7 +477,10 @@ class GPModel(_KernelFit):
         solver's tolerance.  A model fitted with solver="cg" has no bounds: its log det term is
         stochastic Lanczos quadrature on the CG coefficients of nvec Rademacher probes drawn on the
         host from ``seed`` (``rbl.logdet_lanczos``: runs to the fit's tol or min(n, max_iter, 4096)
-        iterations, unpreconditioned), with the standard error over those probes."""
+        iterations, unpreconditioned), with the standard error over those probes.  use_precond=True on
+        a model that holds a preconditioner (``gp_fit`` with precond_rank >= 1, either kind): the
+        quadrature runs preconditioned (``logdet_lanczos(..., precond=)``) — fewer iterations per probe
+        and a smaller standard error; on any other model it changes nothing."""
         from .funm import _trace_on
         n, t = self.y.shape
         with Context(self.device) as ctx:
@@ -485,7 +488,8 @@ class GPModel(_KernelFit):
             if self.solver == "cg":
                 from .solve import MAX_COEF_ITER, logdet_lanczos_on
                 ld, err = logdet_lanczos_on(ctx, nvec, 0.0, seed, max(self.tol, 1e-12),
-                                            min(n, self.max_iter, MAX_COEF_ITER))
+                                            min(n, self.max_iter, MAX_COEF_ITER),
+                                            self.precond if use_precond else None)
                 fit = float(np.sum(self.y * self.alpha))
                 return -0.5 * fit - 0.5 * t * ld - 0.5 * n * t * np.log(2.0 * np.pi), 0.5 * t * err
             ld, err = _trace_on(ctx, np.log, self.bounds[0], self.bounds[1], nvec, None, max(self.tol, 1e-12),
@@ -680,7 +684,7 @@ def _cg_check(what, info, max_iter):
 
 def gp_fit(X, y, *, kind: str = "rbf", gamma: float = 1.0, noise: float, coef0: float = 0.0, degree: int = 3,
            tol: float = 1e-10, bounds=None, device: int = 0, solver: str = "chebyshev", precond_rank: int = 0,
-           max_iter: int = 1000) -> GPModel:
+           max_iter: int = 1000, precond: str = "eig", pchol_rank=None) -> GPModel:
     """Gaussian-process regression on the n points X with targets y (n, or n x t for t outputs) and
     observation noise variance ``noise`` > 0: alpha = (K + noise I)^-1 y by ``apply_function`` with
     f = 1 / x, K never formed; ``predict`` and ``log_marginal_likelihood`` on the model.
@@ -698,7 +702,11 @@ def gp_fit(X, y, *, kind: str = "rbf", gamma: float = 1.0, noise: float, coef0: 
     solves its columns the same way and ``log_marginal_likelihood`` uses Lanczos quadrature on the CG
     coefficients (``rbl.logdet_lanczos``).  precond_rank=r (1..32, solver="cg" only): the r leading
     eigenpairs of K + noise I are computed first (``lanczos``, block size r) and deflated by
-    ``spectral_preconditioner`` — the iteration count then follows the spectrum below them.  A status
+    ``spectral_preconditioner`` — the iteration count then follows the spectrum below them.
+    precond="pchol" (needs solver="cg" and precond_rank >= 1) builds the pair without an eigensolve: a
+    partial pivoted Cholesky factor of K of rank pchol_rank (default min(4 precond_rank, 256, n);
+    ``Context.kernel_pchol``) compressed to its best precond_rank directions by
+    ``pchol_preconditioner(L, noise, precond_rank)``; the model stores the pair as with "eig".  A status
     other than converged raises RBLError (not positive definite) or warns (max_iter reached)."""
     if solver not in ("chebyshev", "cg"):
         raise ValueError('gp_fit: solver must be "chebyshev" or "cg"')
@@ -706,6 +714,16 @@ def gp_fit(X, y, *, kind: str = "rbf", gamma: float = 1.0, noise: float, coef0: 
         raise ValueError("gp_fit: precond_rank must be an integer in [0, 32]")
     if precond_rank and solver != "cg":
         raise ValueError('gp_fit: precond_rank needs solver="cg"')
+    if precond not in ("eig", "pchol"):
+        raise ValueError('gp_fit: precond must be "eig" or "pchol"')
+    if precond == "pchol" and (solver != "cg" or precond_rank < 1):
+        raise ValueError('gp_fit: precond="pchol" needs solver="cg" and precond_rank >= 1')
+    if pchol_rank is not None:
+        if precond != "pchol":
+            raise ValueError('gp_fit: pchol_rank belongs to precond="pchol"')
+        if isinstance(pchol_rank, bool) or not isinstance(pchol_rank, (int, np.integer)) or \
+                not 1 <= pchol_rank <= _lib.RBL_PCHOL_MAX_RANK:
+            raise ValueError(f"gp_fit: pchol_rank must be an integer in [1, {_lib.RBL_PCHOL_MAX_RANK}]")
     if isinstance(noise, bool) or not np.isscalar(noise) or not np.isfinite(noise) or not noise > 0:
         raise ValueError("gp_fit: noise must be a finite number > 0")
     if not np.isscalar(tol) or not 0 < tol < 1:
@@ -724,18 +742,29 @@ def gp_fit(X, y, *, kind: str = "rbf", gamma: float = 1.0, noise: float, coef0: 
             raise ValueError('gp_fit: bounds belong to solver="chebyshev" (CG needs none)')
         if precond_rank > K.n:
             raise ValueError(f"gp_fit: precond_rank = {precond_rank} exceeds n = {K.n}")
+        if pchol_rank is not None and pchol_rank > K.n:
+            raise ValueError(f"gp_fit: pchol_rank = {pchol_rank} exceeds n = {K.n}")
         from .solve import solve_on, spectral_preconditioner
-        precond = None
+        pair = None
         with Context(device) as ctx:
             ctx.set_matrix(K)
-            if precond_rank:
+            if precond_rank and precond == "pchol":
+                from .pchol import pchol_preconditioner
+                R = min(4 * int(precond_rank), _lib.RBL_PCHOL_MAX_RANK, K.n) if pchol_rank is None else int(pchol_rank)
+                L = ctx.kernel_pchol(R)[0]
+                if L.shape[1] < 1:
+                    raise _lib.RBLError(_lib.RBL_ERR_NUMERIC, "gp_fit: the pivoted Cholesky factor of K has rank 0")
+                V, dv = pchol_preconditioner(L, float(noise), int(precond_rank))
+                pair = (np.asfortranarray(V), dv)
+                ctx.set_preconditioner(*pair)
+            elif precond_rank:
                 lam, V, _ = _run(ctx, int(precond_rank), int(precond_rank), None, None, 0)
                 V, dv = spectral_preconditioner(lam, V)
-                precond = (np.asfortranarray(V), dv)
-                ctx.set_preconditioner(*precond)
+                pair = (np.asfortranarray(V), dv)
+                ctx.set_preconditioner(*pair)
             alpha, info = solve_on(ctx, y, tol=tol, max_iter=max_iter)
         _cg_check("gp_fit", info, max_iter)
-        return GPModel(K, shift, device, y, alpha, None, None, float(tol), vec, "cg", precond, int(max_iter))
+        return GPModel(K, shift, device, y, alpha, None, None, float(tol), vec, "cg", pair, int(max_iter))
     from .density import _bounds
     from .funm import apply_function, cheb_fit
     with Context(device) as ctx:

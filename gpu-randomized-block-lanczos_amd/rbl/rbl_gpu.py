@@ -364,6 +364,39 @@ class Context:
                     "rbl_bench_kernel_knn")
         return float(ms[0])
 
+    @staticmethod
+    def _pchol_rank(what, max_rank):
+        if isinstance(max_rank, bool) or not isinstance(max_rank, (int, np.integer)):
+            raise ValueError(f"{what}: max_rank must be an integer")
+        return int(max_rank)
+
+    def kernel_pchol(self, max_rank: int, tol: float = 0.0):
+        """Partial pivoted Cholesky of the kernel matrix held, without its nugget (rbl_kernel_pchol):
+        L L^T ~ diag(s) K diag(s) by at most max_rank (<= min(n, 256)) greedy steps, each one column of
+        K; stops early when the largest residual diagonal entry is at rounding level or the residual
+        trace is <= tol (in [0, 1)) times the first.  Returns (L, piv, trace): L n x rank (F-ordered),
+        piv the rank pivots (int32), trace the rank + 1 residual traces.  Two calls give the same
+        bits."""
+        import ctypes as C
+        R = self._pchol_rank("kernel_pchol", max_rank)
+        n = self.matrix_info()[0]
+        L = np.zeros((n, max(R, 0)), order="F")
+        piv = np.full(max(R, 0), -1, dtype=np.int32)
+        trace = np.zeros(max(R, 0) + 1)
+        rank = C.c_int(0)
+        self._check(lib.rbl_kernel_pchol(self._h, R, float(tol), dptr(L), n, piv.ctypes.data_as(_lib._pi32),
+                                         dptr(trace), C.byref(rank)), "rbl_kernel_pchol")
+        r = int(rank.value)
+        return np.asfortranarray(L[:, :r]), piv[:r].copy(), trace[:r + 1].copy()
+
+    def bench_kernel_pchol(self, max_rank: int, reps: int = 5) -> float:
+        """Milliseconds per factorisation of ``kernel_pchol`` at tol = 0 on the device
+        (rbl_bench_kernel_pchol)."""
+        ms = np.zeros(1)
+        self._check(lib.rbl_bench_kernel_pchol(self._h, self._pchol_rank("bench_kernel_pchol", max_rank), int(reps),
+                                               dptr(ms)), "rbl_bench_kernel_pchol")
+        return float(ms[0])
+
     def kernel_hadamard(self, A, B, Q, weight="value") -> np.ndarray:
         """U (n x b) = (Phi o A B^T) Q over the points of the kernel matrix held
         (rbl_kernel_hadamard): A and B n x r, Q n x b, Phi_ij = kappa (weight "value"), d kappa /

@@ -429,6 +429,35 @@ int rbl_kernel_knn(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int k,
  * one warm-up, then `reps` searches between two hipEvents. */
 int rbl_bench_kernel_knn(rbl_ctx* ctx, int64_t m, const double* Z, int64_t ldz, int k, int splits,
                          int reps, double* ms);
+/* Partial pivoted Cholesky of the kernel matrix held (csrc/pchol.hip): L L^T ~ A = diag(s) K diag(s), the
+ * operator WITHOUT its nugget, from the points alone — a cheap CG preconditioner, landmark selection, a
+ * Nystrom approximation.  With u = 2^-53 and R = max_rank:
+ *   d_i = s_i^2 kappa(x_i, x_i) by the operator's diagonal rule (s_i^2 exactly for rbf and laplace),
+ *   trace_0 = sum_i d_i, dmax0 = max_i d_i, floor = 4 (R + 2) u dmax0;
+ *   step j = 0, 1, ...: the pivot p is the row with the largest d, the smaller index on a tie; stop with
+ *   rank = j when j == R, or !(d_p > floor) (non-positive or NaN values, an indefinite poly kernel, exact
+ *   duplicates), or trace_j <= tol trace_0; otherwise
+ *     L[i, j] = (s_i s_p kappa(x_i, x_p) - sum_{l<j} L[i, l] L[p, l]) / sqrt(d_p)   (l ascending),
+ *     L[p, j] = sqrt(d_p), L[i, j] = 0 exactly where d_i == 0 before the step (earlier pivots, rows whose
+ *     residual was clamped away), d_i <- max(d_i - L[i, j]^2, 0), d_p <- 0, trace_{j+1} = sum_i d_i.
+ * kappa is evaluated in the operator's Gram form in fp64 (one thread per row, ascending coordinates).
+ * One launch per step, R + 1 enqueued back to back with one synchronisation at the end; every sum and
+ * the pivot search run in an order that depends on n alone, without atomics or grid-wide
+ * synchronisation: two calls give the same bits, on any device.  A step moves about 8 n (d4 + j + 3)
+ * bytes, d4 = 4 ceil(d / 4).
+ * L: host n x max_rank column-major, ldl >= n, columns at or beyond the rank zero; piv: max_rank int32,
+ * -1 past the rank; trace: max_rank + 1 doubles (trace_0 .. trace_rank, the last repeated past the
+ * rank); *rank_out the rank.  Any output may be NULL.  Runs on the context's stream (a run in flight is
+ * waited for); device memory for the call only: L, d and the workgroups' partial records.
+ * RBL_ERR_STATE without a kernel matrix; RBL_ERR_INVALID for max_rank outside [1, min(n,
+ * RBL_PCHOL_MAX_RANK)], tol not finite or outside [0, 1), or ldl < n with L given — every rejection
+ * before any allocation, the context unchanged (a following rbl_apply gives the bits of one before). */
+#define RBL_PCHOL_MAX_RANK 256
+int rbl_kernel_pchol(rbl_ctx* ctx, int max_rank, double tol, double* L, int64_t ldl, int32_t* piv,
+                     double* trace, int* rank_out);
+/* Milliseconds per factorisation at tol = 0 (the device part of rbl_kernel_pchol alone): one warm-up,
+ * then `reps` factorisations between two hipEvents. */
+int rbl_bench_kernel_pchol(rbl_ctx* ctx, int max_rank, int reps, double* ms);
 /* Kernel-matrix derivative product over the points of the kernel matrix held:
  *     U (n x b) = (Phi o A B^T) Q,    Phi_ij = phi(x_i, x_j),    (A B^T)_ij = sum_k A_ik B_jk,
  * A and B n x r, Q n x b, host column-major blocks like rbl_kernel_cross (lda, ldb, ldq, ldu >= n).

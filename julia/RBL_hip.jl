@@ -392,6 +392,35 @@ function RBL_gpu_knn(X::Matrix{Float64}, k::Int; Z = nothing, device::Int = 0)
     end
 end
 
+# Partial pivoted Cholesky of the kernel matrix of the rows of X (rbl_kernel_pchol): L L' ~ diag(s) K
+# diag(s), at most max_rank greedy steps, stopping early when the largest residual diagonal entry is at
+# rounding level or the residual trace is <= tol times the first.  Returns (L, piv, trace): L n x rank,
+# piv the pivots (1-based, rank of them), trace the residual traces trace_0 .. trace_rank.  X[piv, :] are
+# landmarks, L L' a Nystrom approximation, and the leading eigenpairs of L L' (a thin QR of L and the
+# SVD of its R) feed rbl_set_preconditioner.  One context: set_matrix!(::KernelPoints), rbl_kernel_pchol,
+# free.
+function RBL_gpu_pchol(X::Matrix{Float64}, max_rank::Int; tol::Float64 = 0.0, kind::Symbol = :rbf,
+                       gamma::Float64 = 1.0, coef0::Float64 = 0.0, degree::Int = 3, scale = nothing,
+                       device::Int = 0)
+    ctx = rbl_context(device)
+    try
+        set_matrix!(ctx, KernelPoints(X, kind, gamma, coef0, degree, scale, 0.0))
+        n = size(X, 1)
+        L = zeros(Float64, n, max_rank)
+        piv = zeros(Int32, max_rank)
+        trace = zeros(Float64, max_rank + 1)
+        rank = Ref{Cint}(0)
+        rbl_check(ctx, ccall((:rbl_kernel_pchol, librbl_hip), Cint,
+                             (Ptr{Cvoid}, Cint, Float64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Cint}),
+                             ctx, Cint(max_rank), tol, L, n, piv, trace, rank),
+                  "rbl_kernel_pchol")
+        r = Int(rank[])
+        return L[:, 1:r], piv[1:r] .+ Int32(1), trace[1:r + 1]
+    finally
+        ccall((:rbl_free, librbl_hip), Cint, (Ptr{Cvoid},), ctx)
+    end
+end
+
 # k-means of the rows of X (n x d) into c clusters on the device (rbl_kmeans_*): Lloyd's iteration from
 # the centres `init` (c x d), or with init = nothing from plain k-means++ seeding on the device with the c
 # uniforms rand(Random.MersenneTwister(seed), c).  A point goes to the centre with the smallest (squared

@@ -16,6 +16,7 @@ Writes one JSON document (default profiles/kernelop_bench.json).
 --cross times the cross-kernel product kappa(Z, X) W (kernelop_cross.hip) instead: see cross();
 --hadamard the derivative product (Phi o A B^T) Q (kernelop_hadamard.hip): see hadamard();
 --knn the k-nearest-neighbour search (kernelop_knn.hip): see knn();
+--pchol the partial pivoted Cholesky factorisation (pchol.hip) and the GP fit it preconditions: see pchol();
 --kmeans one Lloyd iteration (kmeans.hip) and the labels' share of spectral clustering: see kmeans()."""
 import argparse
 import json
@@ -210,6 +211,98 @@ def blobs(n, d, c, seed=0):
     return np.asfortranarray(X), X[np.arange(c) * (n // c)].copy()
 
 
+def pchol(args):
+    """--pchol: rbl_bench_kernel_pchol (hipEvents around `--reps` factorisations at tol = 0 after one
+    warm-up) for each (n, d, R) of --pchol-shapes, beside rbl_bench_kernel_pass of the symmetric
+    operator over the same points at b = 32 from the same process (the two alternate within a round;
+    medians over `--rounds` rounds), and the byte model sum_{j<R} 8 n (d4 + j + 3).  With --pchol-gp N the
+    GP fit of tools/bench_solve.py (N points in three blobs, d = 2, rbf --gamma, --pchol-noise, tol
+    --pchol-tol, one column) with its preconditioner built three ways in one process — 32 eigenpairs by
+    block Lanczos (gp_fit's precond="eig"), and a pivoted Cholesky factor of rank 32 and of rank 128
+    compressed to 32 directions (precond="pchol") — each as gp_fit runs it, timed in its parts: the
+    set-up of the pair (for the factor: the device call, and the host QR + SVD of pchol_eigenpairs
+    apart), the CG solve with its iteration count, and the wall time of the gp_fit call itself."""
+    if len(args.pchol_shapes) % 3:
+        raise SystemExit("--pchol-shapes takes n d R triples")
+    shapes = [tuple(args.pchol_shapes[i:i + 3]) for i in range(0, len(args.pchol_shapes), 3)]
+
+    import rbl
+
+    doc = {"reps": args.reps, "rounds": args.rounds, "pchol": []}
+    for n, d, R in shapes:
+        d4 = 4 * ((d + 3) // 4)
+        with rbl.Context(0) as ctx:
+            ctx.set_matrix_kernel(points(n, d), "rbf", args.gamma)
+            rank = ctx.kernel_pchol(R)[1].size
+            runs = {"pchol": lambda: ctx.bench_kernel_pchol(R, reps=args.reps),
+                    "symmetric_b32": lambda: ctx.bench_kernel_pass(32, args.reps)}
+            for fn in runs.values():
+                fn()                                              # warm both once
+            times = {name: [] for name in runs}
+            for _ in range(args.rounds):
+                for name, fn in runs.items():
+                    times[name].append(fn())
+        row = {"n": n, "d": d, "max_rank": R, "rank": int(rank), "launches": R + 2}
+        for name, t in times.items():
+            row[f"ms_{name}"] = statistics.median(t)
+            row[f"ms_{name}_rounds"] = t
+        row["model_bytes"] = 8 * n * (R * (d4 + 3) + R * (R - 1) // 2)
+        row["tb_per_s"] = row["model_bytes"] / (row["ms_pchol"] * 1e-3) / 1e12
+        row["us_per_step"] = 1e3 * row["ms_pchol"] / (R + 2)
+        row["pchol_over_symmetric_b32"] = row["ms_pchol"] / row["ms_symmetric_b32"]
+        doc["pchol"].append(row)
+        print(json.dumps(row), flush=True)
+    if args.pchol_gp:
+        from rbl.kernelop import _centred_kernel, _run
+        from rbl.solve import solve_on, spectral_preconditioner
+        n, noise, tol = args.pchol_gp, args.pchol_noise, args.pchol_tol
+        rng = np.random.default_rng(0)
+        X = 3.0 * rng.standard_normal((3, 2))[np.arange(n) % 3] + 0.35 * rng.standard_normal((n, 2))
+        X -= X.mean(axis=0)
+        y = (np.sin(X[:, 0]) + 0.1 * np.random.default_rng(1).standard_normal(n))[:, None]
+        K, _ = _centred_kernel("bench", X, "rbf", args.gamma, 0.0, 3, nugget=noise)
+        doc["gp"] = {"n": n, "d": 2, "gamma": args.gamma, "noise": noise, "tol": tol, "routes": {}}
+        rbl.gp_fit(X[:2048], y[:2048, 0], gamma=args.gamma, noise=noise, tol=tol, solver="cg", precond_rank=8)  # warm-up
+        for name, kw in (("none", {}), ("eig32", {"precond_rank": 32}),
+                         ("pchol32", {"precond": "pchol", "precond_rank": 32, "pchol_rank": 32}),
+                         ("pchol128", {"precond": "pchol", "precond_rank": 32, "pchol_rank": 128})):
+            row = {}
+            with rbl.Context(0) as ctx:                           # the steps of gp_fit, timed apart
+                ctx.set_matrix(K)
+                t0 = time.perf_counter()
+                if name.startswith("eig"):
+                    lam, V, _ = _run(ctx, 32, 32, None, None, 0)
+                    pair = spectral_preconditioner(lam, V)
+                elif name.startswith("pchol"):
+                    L = ctx.kernel_pchol(kw["pchol_rank"])[0]
+                    row["seconds_device_factor_and_copy"] = time.perf_counter() - t0
+                    t1 = time.perf_counter()
+                    rbl.pchol_eigenpairs(L, min(32, L.shape[1]))
+                    row["seconds_host_qr_svd"] = time.perf_counter() - t1
+                    t0 += time.perf_counter() - t1                 # (run once more inside pchol_preconditioner)
+                    pair = rbl.pchol_preconditioner(L, noise, 32)
+                    row["rank"] = int(L.shape[1])
+                else:
+                    pair = None
+                if pair is not None:
+                    ctx.set_preconditioner(np.asfortranarray(pair[0]), pair[1])
+                row["seconds_setup"] = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                _, info = solve_on(ctx, y, tol=tol, max_iter=args.pchol_max_iter)
+                row["seconds_solve"] = time.perf_counter() - t0
+                row.update(iters=int(info.iters[0]), status=int(info.status[0]), resid=float(info.residual[0]))
+            t0 = time.perf_counter()
+            rbl.gp_fit(X, y[:, 0], gamma=args.gamma, noise=noise, tol=tol, solver="cg", max_iter=args.pchol_max_iter, **kw)
+            row["seconds_gp_fit"] = time.perf_counter() - t0
+            doc["gp"]["routes"][name] = row
+            print(name, json.dumps(row), flush=True)
+    out = args.out if args.out else os.path.join(ROOT, "profiles", "kernelop_pchol_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", out)
+
+
 def kmeans(args):
     """--kmeans: rbl_bench_kmeans_iter (hipEvents around `--reps` Lloyd iterations after one warm-up)
     for each (n, d, c) of --kmeans-shapes, beside two yardsticks from the same process: the k = 1
@@ -280,6 +373,16 @@ def main():
                     help="n d c triples of --kmeans")
     ap.add_argument("--kmeans-e2e", type=int, default=0,
                     help="with --kmeans: also the wall time of RBL_spectral_clustering over this many points")
+    ap.add_argument("--pchol", action="store_true",
+                    help="time the pivoted Cholesky factorisation instead (profiles/kernelop_pchol_bench.json)")
+    ap.add_argument("--pchol-shapes", type=int, nargs="+",
+                    default=[32768, 16, 32, 32768, 16, 128, 32768, 16, 256, 131072, 16, 32, 131072, 16, 128,
+                             131072, 16, 256], help="n d R triples of --pchol")
+    ap.add_argument("--pchol-gp", type=int, default=0,
+                    help="with --pchol: also the GP fit over this many points, preconditioned three ways")
+    ap.add_argument("--pchol-noise", type=float, default=1e-2)
+    ap.add_argument("--pchol-tol", type=float, default=1e-8)
+    ap.add_argument("--pchol-max-iter", type=int, default=2000)
     ap.add_argument("--knn", action="store_true",
                     help="time the neighbour search instead (profiles/kernelop_knn_bench.json)")
     ap.add_argument("--knn-shapes", type=int, nargs="+", default=[32768, 16, 16, 131072, 16, 16],
@@ -309,6 +412,8 @@ def main():
     args = ap.parse_args()
     if args.kmeans:
         return kmeans(args)
+    if args.pchol:
+        return pchol(args)
     if args.knn:
         return knn(args)
     if args.cross:
